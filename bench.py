@@ -1,7 +1,7 @@
 """Benchmark: reproject bilinear EPSG:4326 -> EPSG:3857, 40960x40960 float32,
 2048x2048 target tiles (BASELINE.json metric, configs[4]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (driver, N > 1)
 
 `python bench.py --gpus N` with N > 1 outside torchrun starts the N ranks
@@ -29,11 +29,20 @@ load to ramp from ~1.6 to ~2.38 GHz and K1 follows the clock
 the clock measured just before and just after the timed steps.
 `roofline.achieved` = algorithmic bytes of all ranks (output + distinct
 source pixels read, x4 B) / max-over-ranks kernel time (HIP events on the
-launch stream); `peak` = N x 8 TB/s.  `traffic` = FETCH_SIZE + WRITE_SIZE per
-launch from two rocprofv3 --pmc child passes of this workload before the
-bench touches the GPU (N = 1): the L2's memory-side requests counted by size,
-with three launches of known bytes beside it (scripts/pmc_traffic.py).
-Rank 0 prints ONE JSON line.
+launch stream); `peak` = N x 8 TB/s.  Rank 0 prints ONE JSON line.
+
+A plain run does only that: set-up, the copy rate, W warm-up steps, K timed
+steps, the line.  `--dump-outputs DIR` also writes what the last timed step
+left in the output raster as DIR/reproject_bilinear.npy (dump_outputs: the
+whole array up to 64 MB, else a fixed seeded sample of it; the inputs are
+seeded, so two builds can be compared output for output).  `--full` adds the
+measurements that take runs of their own (N = 1; each can be switched off
+again with its --no-... option): `roofline.traffic` = FETCH_SIZE + WRITE_SIZE
+per launch from two rocprofv3 --pmc child passes of this workload before the
+bench touches the GPU, the L2's memory-side requests counted by size, with
+three launches of known bytes beside it (scripts/pmc_traffic.py);
+`cpu_baseline`, the oracle on host threads; `f64_out`, the same steps with
+float64 output.
 """
 
 from __future__ import annotations
@@ -59,6 +68,8 @@ METRIC = "Mpixels/s reproject bilinear 40960² f32; achieved HBM GB/s vs peak"
 SRC_X0, SRC_Y0 = -20.0, 70.96
 TGT_MIN = (-2226000.0, 3504000.0)
 GEN_ROWS = 1024          # the synthetic raster is generated in seeded 1024-row chunks
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs writes at most this much, all ranks together
+DUMP_SAMPLE = 1 << 22       # elements of the sample of an output larger than that
 
 
 def workload(size: int, tile: int):
@@ -120,6 +131,36 @@ def synthetic_rows(j0: int, j1: int, width: int, device, seed: int = 20250905):
         if b > a:
             out[:, a - j0:b - j0] = chunk[:, a - c0:b - c0]
     return out
+
+
+def dump_sample_index(numel: int, itemsize: int, world: int = 1, seed: int = 20250906):
+    """Which elements of a rank's flattened output --dump-outputs writes: None
+    (all of them) when every rank's share fits in DUMP_MAX_BYTES together,
+    else DUMP_SAMPLE / world sorted flat indices drawn with a fixed seed (the
+    same elements in every run with the same arguments)."""
+    if numel * itemsize * world <= DUMP_MAX_BYTES:
+        return None
+    rng = np.random.default_rng(seed)
+    return np.sort(rng.integers(0, numel, DUMP_SAMPLE // world))
+
+
+def dump_outputs(directory: str, out, rank: int = 0, world: int = 1) -> str:
+    """Write the output raster `out` (a torch tensor, float32 or float64: what
+    the timed path's caller receives) as `directory`/reproject_bilinear.npy
+    (N > 1: ..._rank<r>.npy, each rank its own band), whole or sampled
+    (dump_sample_index).  Returns the path."""
+    import torch
+
+    idx = dump_sample_index(out.numel(), out.element_size(), world)
+    if idx is None:
+        arr = out.cpu().numpy()
+    else:
+        arr = out.reshape(-1)[torch.from_numpy(idx).to(out.device)].cpu().numpy()
+    os.makedirs(directory, exist_ok=True)
+    name = "reproject_bilinear" + (f"_rank{rank}" if world > 1 else "")
+    path = os.path.join(directory, name + ".npy")
+    np.save(path, arr)
+    return path
 
 
 def cpu_baseline(plan, tgm, seconds: float = 12.0, sweep=(1, 32, 128), sweep_seconds=3.0):
@@ -386,12 +427,20 @@ def main():
     ap.add_argument("--size", type=int, default=40960)
     ap.add_argument("--tile", type=int, default=2048)
     ap.add_argument("--out-dtype", choices=["f32", "f64"], default="f32")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the output raster of the last step to "
+                         "DIR/reproject_bilinear.npy (whole up to 64 MB, else a fixed seeded "
+                         "sample)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own (one GPU): the rocprofv3 "
+                         "--pmc traffic passes, the CPU baseline, float64 output")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--no-traffic", action="store_true",
-                    help="skip the two rocprofv3 --pmc passes (traffic: null)")
+                    help="with --full: skip the two rocprofv3 --pmc passes (traffic: null)")
     ap.add_argument("--no-f64", action="store_true",
-                    help="skip the secondary measurement with float64 output")
+                    help="with --full: skip the secondary measurement with float64 output")
     ap.add_argument("--no-graph", action="store_true",
                     help="launch every step eagerly instead of replaying a captured hipGraph")
     ap.add_argument("--shard", choices=["bands", "slices"], default="bands",
@@ -409,6 +458,8 @@ def main():
                          "collectives, JSON line with the ranks block): no GPU, no kernel; "
                          "value and roofline are null")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     from xcube_resampling_amd.sharding import band_shard, env_rank, max_over_ranks
 
@@ -418,7 +469,9 @@ def main():
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
     dry = args.dry_run
     if dry:
-        args.no_traffic = args.no_cpu_baseline = args.no_f64 = args.no_graph = True
+        args.no_graph = True
+    if dry or not args.full:
+        args.no_traffic = args.no_cpu_baseline = args.no_f64 = True
     # PMC passes first: child processes, before this process initialises HIP
     traffic = None
     if world == 1 and not args.no_traffic:
@@ -541,6 +594,8 @@ def main():
     ms_per_step, kernel_ms, clocks = timed(make_step(out, out_np), args.steps, args.warmup)
     if flags is not None:
         flags.raise_if_set("bench reproject")
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, out, rank, world)
 
     copy_gbs = copy_rates[0]
     s_read = source_pixels_read(plan, rows) if rows[1] > rows[0] else 0

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 O=${1:-gpurun_out/k1cg}; mkdir -p $O
 timeout -k 10 600 python -u -m pytest tests/test_reproject_gpu.py tests/test_configs_gpu.py tests/test_sharding_gpu.py tests/test_streaming_gpu.py -q -x --timeout 300 --timeout-method thread > $O/pytest.log 2>&1 || { tail -30 $O/pytest.log; exit 1; }
 tail -1 $O/pytest.log
-B="bench.py --no-cpu-baseline --no-traffic --steps 30 --warmup 10"
+B="bench.py --full --no-cpu-baseline --no-traffic --steps 30 --warmup 10"
 for pass in 1 2; do
   for arm in base k1old k1g1 k1g2 k1g8; do
     if [ $arm = base ]; then L=xcube-resampling_amd/lib/libxrs.so; else L=probe/$arm/pkg/lib/libxrs.so; fi

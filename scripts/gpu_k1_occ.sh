@@ -10,7 +10,7 @@ for arm in $ARMS; do
   XRS_LIBRARY=$(lib $arm) timeout -k 10 180 python -u scripts/k1_hash.py > $O/hash_$arm.txt 2> $O/hash_$arm.err || exit $?
   echo "hash $arm $(cat $O/hash_$arm.txt)"
 done
-B="bench.py --no-cpu-baseline --no-traffic --steps 30 --warmup 10"
+B="bench.py --full --no-cpu-baseline --no-traffic --steps 30 --warmup 10"
 for pass in $(seq 1 $PASSES); do
   for arm in $ARMS; do
     XRS_LIBRARY=$(lib $arm) timeout -k 10 300 python -u $B > $O/ab_${arm}_$pass.json 2> $O/ab_${arm}_$pass.err || exit $?
@@ -19,6 +19,6 @@ for pass in $(seq 1 $PASSES); do
 done
 # the traffic of an arm (bench line with its two PMC passes)
 if [ -n "$TRAFFIC_ARM" ]; then
-  XRS_LIBRARY=$(lib $TRAFFIC_ARM) timeout -k 10 600 python -u bench.py --no-cpu-baseline --warmup 5 > $O/traffic_$TRAFFIC_ARM.json 2> $O/traffic_$TRAFFIC_ARM.err || exit $?
+  XRS_LIBRARY=$(lib $TRAFFIC_ARM) timeout -k 10 600 python -u bench.py --full --no-cpu-baseline --warmup 5 > $O/traffic_$TRAFFIC_ARM.json 2> $O/traffic_$TRAFFIC_ARM.err || exit $?
   cut -c1-300 $O/traffic_$TRAFFIC_ARM.json
 fi

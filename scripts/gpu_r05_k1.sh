@@ -13,5 +13,5 @@ for pass in 1 2 3; do
     tail -1 $O/ab.jsonl
   done
 done
-timeout -k 10 600 python -u bench.py --gpus 1 --warmup 5 --steps 20 > $O/bench_w5.json 2> $O/bench_w5.err || exit $?
+timeout -k 10 600 python -u bench.py --full --gpus 1 --warmup 5 --steps 20 > $O/bench_w5.json 2> $O/bench_w5.err || exit $?
 cut -c1-400 $O/bench_w5.json

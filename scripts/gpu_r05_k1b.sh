@@ -16,6 +16,6 @@ for pass in 1 2 3; do
 done
 for arm in base k1nox k1tab; do
   if [ $arm = base ]; then L=xcube-resampling_amd/lib/libxrs.so; else L=probe/$arm/pkg/lib/libxrs.so; fi
-  XRS_LIBRARY=$L timeout -k 10 400 python -u bench.py --gpus 1 --warmup 5 --steps 20 --no-cpu-baseline --no-f64 > $O/bench_$arm.json 2> $O/bench_$arm.err || exit $?
+  XRS_LIBRARY=$L timeout -k 10 400 python -u bench.py --full --gpus 1 --warmup 5 --steps 20 --no-cpu-baseline --no-f64 > $O/bench_$arm.json 2> $O/bench_$arm.err || exit $?
   cut -c1-200 $O/bench_$arm.json
 done

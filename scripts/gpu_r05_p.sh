@@ -18,5 +18,5 @@ for pass in 1 2 3; do
 done
 timeout -k 10 600 python -u scripts/bench_configs.py --configs 2 --cpu-seconds 4 > $O/config2.jsonl 2> $O/config2.err || { tail -20 $O/config2.err; exit 1; }
 cut -c1-300 $O/config2.jsonl
-timeout -k 10 600 python -u bench.py --gpus 1 --warmup 5 --steps 20 > $O/bench_w5.json 2> $O/bench_w5.err || exit $?
+timeout -k 10 600 python -u bench.py --full --gpus 1 --warmup 5 --steps 20 > $O/bench_w5.json 2> $O/bench_w5.err || exit $?
 cut -c1-300 $O/bench_w5.json

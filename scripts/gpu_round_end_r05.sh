@@ -10,7 +10,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -q -x --timeout 300 --timeout
 tail -3 $OUT/pytest_gpu.log
 if [ $rc -ne 0 ]; then echo "pytest ended with status $rc"; exit $rc; fi
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || exit $?
-timeout -k 10 600 python -u bench.py --gpus 1 --warmup 5 --steps 20 > $OUT/bench_w5.json 2> $OUT/bench_w5.err || exit $?
+timeout -k 10 600 python -u bench.py --full --gpus 1 --warmup 5 --steps 20 > $OUT/bench_w5.json 2> $OUT/bench_w5.err || exit $?
 cut -c1-300 $OUT/bench_w5.json
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o bench -- python3 bench.py --no-cpu-baseline --no-traffic --no-f64 --warmup 5 > $OUT/bench_prof.json 2> $OUT/bench_prof.err || exit $?
 cut -c1-200 $OUT/bench_prof.json

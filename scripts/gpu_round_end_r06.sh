@@ -14,7 +14,7 @@ tail -3 $OUT/pytest_gpu.log
 if [ $rc -ne 0 ]; then echo "pytest ended with status $rc"; exit $rc; fi
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || exit $?
 tail -1 $OUT/smoke.log
-timeout -k 10 600 python -u bench.py --gpus 1 --warmup 5 --steps 20 > $OUT/bench_w5.json 2> $OUT/bench_w5.err || exit $?
+timeout -k 10 600 python -u bench.py --full --gpus 1 --warmup 5 --steps 20 > $OUT/bench_w5.json 2> $OUT/bench_w5.err || exit $?
 cut -c1-300 $OUT/bench_w5.json
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o bench -- python3 bench.py --no-cpu-baseline --no-traffic --no-f64 --warmup 5 > $OUT/bench_prof.json 2> $OUT/bench_prof.err || exit $?
 cut -c1-200 $OUT/bench_prof.json
@@ -23,6 +23,6 @@ cut -c1-160 $OUT/configs.jsonl
 timeout -k 10 300 python -u scripts/rehearse_bands.py > $OUT/bands.jsonl 2> $OUT/bands.err || exit $?
 cut -c1-200 $OUT/bands.jsonl
 for n in 2 4; do
-  XRS_BENCH_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29600 + n)) bench.py --gpus $n --warmup 3 --steps 5 --no-cpu-baseline --no-f64 > $OUT/bench_gloo$n.json 2> $OUT/bench_gloo$n.err || exit $?
+  XRS_BENCH_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29600 + n)) bench.py --full --gpus $n --warmup 3 --steps 5 --no-cpu-baseline --no-f64 > $OUT/bench_gloo$n.json 2> $OUT/bench_gloo$n.err || exit $?
   cut -c1-300 $OUT/bench_gloo$n.json
 done

@@ -136,6 +136,40 @@ def test_gpus_flag_launches_the_ranks_itself():
     assert line["value"] is None and line["roofline"] is None and "dry_run" in line
 
 
+def test_dump_sample_index_is_fixed_and_bounded():
+    """--dump-outputs writes a small output whole and, of a larger one, the
+    same seeded sample in every run; all ranks together stay within 64 MB."""
+    import bench
+
+    assert bench.dump_sample_index(4096 * 4096, 4) is None          # exactly 64 MB
+    assert bench.dump_sample_index(4096 * 4096, 8) is not None
+    n = 40960 * 40960
+    for world in (1, 8):
+        idx = bench.dump_sample_index(n // world, 8, world)
+        assert np.array_equal(idx, bench.dump_sample_index(n // world, 8, world))
+        assert idx.dtype == np.int64 and (np.diff(idx) >= 0).all()
+        assert 0 <= idx[0] and idx[-1] < n // world
+        assert idx.size * 8 * world <= bench.DUMP_MAX_BYTES
+        assert idx.size * world >= 1 << 20
+
+
+def test_plain_run_line_and_dump_outputs(tmp_path):
+    """A plain run (host-only rehearsal) prints the headline keys and none of
+    the measurements behind --full, and --dump-outputs writes the output
+    raster of the timed path as one float32 .npy file."""
+    d = tmp_path / "dump"
+    r, line = _run_bench(["--gpus", "1", "--dry-run", "--size", "2048", "--tile", "512",
+                          "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)])
+    assert r.returncode == 0, r.stderr[-3000:]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] >= 0
+    assert not {"cpu_baseline", "f64_out"} & set(line)
+    assert [f.name for f in d.iterdir()] == ["reproject_bilinear.npy"]
+    a = np.load(d / "reproject_bilinear.npy")
+    assert a.dtype == np.float32 and a.shape == (1, 2048, 2048)
+
+
 def test_gpus_flag_refuses_more_ranks_than_gpus():
     """Without enough visible GPUs (none here) `--gpus 4` exits non-zero with
     the exact torchrun command instead of measuring one GPU."""

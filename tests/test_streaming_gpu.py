@@ -294,6 +294,19 @@ def test_host_register_copy_unregister_then_fresh_pageable_copy():
 
     lib = _native.lib()
     page = mmap.PAGESIZE
+    # some hosts refuse to page-lock memory a process already owns (hipHostRegister
+    # returns an error for any range): found out on one page, before any work
+    torch.cuda.synchronize()
+    probe = np.frombuffer(mmap.mmap(-1, page), dtype=np.uint8)
+    rc = lib.xrs_host_register(ctypes.c_void_p(probe.ctypes.data), page)
+    if rc == _native.XRS_ERR_HIP:
+        pytest.skip("needs a host that can page-lock existing memory: "
+                    + lib.xrs_last_error().decode())
+    assert rc == _native.XRS_OK
+    streams = (ctypes.c_void_p * 1)(torch.cuda.current_stream().cuda_stream)
+    _native.check(lib.xrs_host_unregister(ctypes.c_void_p(probe.ctypes.data), streams, 1),
+                  "xrs_host_unregister")
+    del probe
     nbytes = 64 * (1 << 20)
     assert nbytes % page == 0
     dev = torch.empty(nbytes // 4, dtype=torch.float32, device="cuda")
