@@ -53,6 +53,7 @@ extern "C" {
 #define XRS_INTERP_NEAREST 0
 #define XRS_INTERP_BILINEAR 1
 #define XRS_INTERP_TRIANGULAR 2
+#define XRS_INTERP_BICUBIC 3   /* xrs_reproject only (not the reference's: an engine extension) */
 
 /* ---- err_flags bits ------------------------------------------------------ */
 #define XRS_EFLAG_INDEX 1     /* numpy IndexError (window index out of range) */
@@ -118,6 +119,26 @@ int xrs_copy_async(void* dst, const void* src, int64_t bytes, void* stream);
  *   outside [0,src_h) x [0,src_w) -> fill (the da.pad constant).
  *   nearest: rint (half-even); bilinear: f64 lerps, source differences in the
  *   source dtype; triangular: two-triangle plane, stored in the source dtype.
+ *   bicubic (XRS_INTERP_BICUBIC): Keys cubic convolution, a = -0.5 (Catmull-
+ *   Rom, GDAL's `cubic`), sampled at bilinear's positions.  Per axis f, c, d
+ *   are bilinear's: the global source index of floor(i) and of ceil(i) after
+ *   the int16 window index and its wrap (XRS_EFLAG_INDEX as above), and
+ *   d = i - (double)(int16)floor(i).  If f or c lies outside the source on
+ *   either axis the pixel is `fill` (converted to dst_dtype).  Otherwise the
+ *   taps of the axis are the global indices f-1, f, f+1, f+2, each clamped to
+ *   [0, size-1] (edge replicate; the tile window plays no further part); a
+ *   tap row outside the band held on the device sets XRS_EFLAG_BAND.  In
+ *   float64, without contraction, in this order:
+ *     w0 = ((-0.5*d + 1.0)*d - 0.5)*d      w1 = (1.5*d - 2.5)*(d*d) + 1.0
+ *     w2 = ((-1.5*d + 2.0)*d + 0.5)*d      w3 = (0.5*d - 0.5)*(d*d)
+ *     h_j = ((w0x*v_j0 + w1x*v_j1) + w2x*v_j2) + w3x*v_j3    (tap row j, taps
+ *                                                        converted to float64)
+ *     out = ((w0y*h_0 + w1y*h_1) + w2y*h_2) + w3y*h_3
+ *   NaN propagates by the arithmetic (a zero weight does not mask it); a
+ *   float32 result is the float64 one rounded once.  Separable modes (0, 2)
+ *   filter every source row once per work item and column (K1q, a rolling
+ *   ring of four h rows); coord_mode 1 reads the 16 taps per pixel.
+ *   xrs_reproject_proj does not take this code.
  *
  * src: (n, src_rows, src_w) with element strides (src_sn, src_sy, 1); row 0
  *      of the buffer is global source row `src_row0` (a device may hold a band).
@@ -127,7 +148,8 @@ int xrs_copy_async(void* dst, const void* src, int64_t bytes, void* stream);
  *      each tile's window in unpadded source indices): device memory,
  *      ntiles = ceil(dst_h/tile_h) * ceil(dst_w/tile_w), row-major.
  * dst_dtype: = src_dtype for nearest/triangular; float32 or float64 for
- *      bilinear (the reference yields float64 there; float32 = declared dtype).
+ *      bilinear and bicubic (the reference yields float64 for bilinear;
+ *      float32 = declared dtype).
  * workspace: device scratch of xrs_reproject_workspace_size(...) bytes; 0
  *      since round 5 (K1's work items resolve their own axis entries), so
  *      NULL / 0 may be passed.

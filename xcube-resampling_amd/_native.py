@@ -54,6 +54,12 @@ XRS_EFLAG_INF_TO_INT = 8
 XRS_EFLAG_STATE = 16
 
 INTERP_CODES = {"nearest": 0, "bilinear": 1, "triangular": 2}
+# xrs_reproject alone also takes bicubic (XRS_INTERP_BICUBIC); rectify and the
+# affine path keep INTERP_CODES and so keep rejecting it
+REPROJECT_INTERP_CODES = {**INTERP_CODES, "bicubic": 3}
+# source rows beyond the floor / ceil rows a method's taps reach, per side
+# (ReprojectPlan.source_rows_read and friends)
+REPROJECT_HALO = {"bicubic": 1}
 
 DTYPE_CODES = {
     np.dtype(np.uint8): 1,

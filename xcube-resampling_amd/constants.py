@@ -19,7 +19,7 @@ AggMethods: TypeAlias = AggMethod | Mapping[np.dtype | str, AggMethod]
 AGG_METHOD_NAMES = ("center", "count", "first", "last", "prod", "max", "mean", "median",
                     "min", "mode", "std", "sum", "var")
 InterpMethodInt = Literal[0, 1]
-InterpMethodStr = Literal["nearest", "triangular", "bilinear"]
+InterpMethodStr = Literal["nearest", "triangular", "bilinear", "bicubic"]
 InterpMethod = InterpMethodInt | InterpMethodStr
 InterpMethods: TypeAlias = InterpMethod | Mapping[np.dtype | Hashable, InterpMethod]
 INTERP_METHOD_MAPPING = {0: "nearest", 1: "bilinear", "nearest": 0, "bilinear": 1}

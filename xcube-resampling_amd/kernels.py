@@ -65,14 +65,14 @@ def reproject(src, plan, interp: str, fill: float, out_dtype=None, rows=None, ou
     if w != plan.src_width:
         raise ValueError(f"source width {w} does not match the plan ({plan.src_width})")
     src_dtype = _native.DTYPE_CODES[_np_dtype(src)]
-    interp_code = _native.INTERP_CODES.get(interp)
+    interp_code = _native.REPROJECT_INTERP_CODES.get(interp)
     if interp_code is None:
         raise NotImplementedError(
             f"interp_methods must be one of 0, 1, 'nearest', 'bilinear', 'triangular', "
             f"was '{interp}'."
         )
     if out_dtype is None:
-        out_dtype = np.float64 if interp == "bilinear" else _np_dtype(src)
+        out_dtype = np.float64 if interp in ("bilinear", "bicubic") else _np_dtype(src)
     r0, r1 = (0, plan.dst_height) if rows is None else rows
     if h_band == 0:
         # a band that reads no source row (all taps in the padding): K1 still
@@ -80,7 +80,7 @@ def reproject(src, plan, interp: str, fill: float, out_dtype=None, rows=None, ou
         src = torch().zeros((n, 1, w), dtype=src.dtype, device=device)
     if out is None:
         out = empty((n, r1 - r0, plan.dst_width), out_dtype, device)
-    if plan.fused_transform(device):
+    if plan.fused_transform(device, interp):
         return _reproject_proj(src, h_band, plan, interp_code, fill, out_dtype, r0, r1, out,
                                src_row0, flags, check, stream)
     tables = plan.device_tables(device)

@@ -24,7 +24,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from . import kernels, multidevice, streaming
+from . import _native, kernels, multidevice, streaming
 from .constants import SCALE_LIMIT
 from .crs import Transformer
 from .dataset import DataArray, Dataset
@@ -112,10 +112,14 @@ class ReprojectPlan:
             self._device_cache[key] = tabs
         return tabs
 
-    def fused_transform(self, device) -> bool:
+    def fused_transform(self, device, interp: str | None = None) -> bool:
         """True when the next K1 call evaluates the transformation per pixel:
         a 2-D plan without coordinate tables on `device` whose tables would
-        exceed ``reproject_table_max_bytes`` (or ``fuse_transform`` set)."""
+        exceed ``reproject_table_max_bytes`` (or ``fuse_transform`` set).
+        Never for ``interp`` "bicubic": the fused kernel has no bicubic
+        variant, such plans go through coordinate tables whatever their size."""
+        if interp == "bicubic":
+            return False
         if self.coord_mode != 1 or self.src_x is not None or str(device) in self._device_cache:
             return False
         table_bytes = 16 * self.dst_width * self.dst_height
@@ -152,12 +156,23 @@ class ReprojectPlan:
             self._device_cache[key] = ws
         return ws
 
-    def _row_read_grid(self):
+    def _row_read_grid(self, halo: int = 0):
         """(H', ntiles_x) int64 arrays (lo, hi) of the global source rows the
         floor / ceil taps of each target row read in each tile column
         (reproject.py:279, 286-291, 316-321: int16 window index with
         python-style wrap, window origin, rows outside the source read the
-        pad and are not counted); lo > hi where nothing is read."""
+        pad and are not counted); lo > hi where nothing is read.
+        ``halo`` > 0 (bicubic: 1): the extent of a method whose taps reach
+        `halo` rows beyond the floor row and the row after it — lo - halo and
+        max(hi, lo + 1) + halo (the ceil row is the floor row itself at an
+        integer position, the taps still reach floor + 2), clamped to the
+        source."""
+        if halo:
+            lo, hi = self._row_read_grid()
+            ok = hi >= lo
+            lo_h = np.where(ok, np.maximum(lo - halo, 0), lo)
+            hi_h = np.where(ok, np.minimum(np.maximum(hi, lo + 1) + halo, self.src_height - 1), hi)
+            return lo_h, hi_h
         cache = self._device_cache.get("row_read_grid")
         if cache is not None:
             return cache
@@ -180,12 +195,13 @@ class ReprojectPlan:
         self._device_cache["row_read_grid"] = (lo, hi)
         return lo, hi
 
-    def row_source_extent(self) -> tuple[np.ndarray, np.ndarray]:
+    def row_source_extent(self, halo: int = 0) -> tuple[np.ndarray, np.ndarray]:
         """Per target row: the lowest and highest global source row read
-        (lo > hi: none).  Separable plans only."""
+        (lo > hi: none), widened by ``halo`` (``_row_read_grid``).  Separable
+        plans only."""
         if self.coord_mode != 0:
             raise NotImplementedError("row extents need separable coordinate tables")
-        lo, hi = self._row_read_grid()
+        lo, hi = self._row_read_grid(halo)
         return lo.min(axis=1), hi.max(axis=1)
 
     def source_cols_read(self) -> int:
@@ -206,26 +222,30 @@ class ReprojectPlan:
                 cols[g[ok]] = True
         return int(cols.sum())
 
-    def source_rows_read(self, r0: int, r1: int) -> tuple[int, int]:
+    def source_rows_read(self, r0: int, r1: int, halo: int = 0) -> tuple[int, int]:
         """Global source rows [j0, j1) that K1 reads for target rows [r0, r1)
         — exactly (separable plans) or the union of the tile windows
-        (2-D coordinate plans)."""
+        (2-D coordinate plans); ``halo``: the method's reach beyond the floor
+        and ceil rows (bicubic: 1)."""
         if self.coord_mode != 0:
-            return self.source_rows_for(r0, r1)
-        lo, hi = self.row_source_extent()
+            return self.source_rows_for(r0, r1, halo)
+        lo, hi = self.row_source_extent(halo)
         lo, hi = lo[r0:r1], hi[r0:r1]
         ok = hi >= lo
         if not ok.any():
             return 0, 0
         return int(lo[ok].min()), int(hi[ok].max()) + 1
 
-    def source_rows_for(self, r0: int, r1: int) -> tuple[int, int]:
-        """Global source rows [j0, j1) read by target rows [r0, r1) (clipped)."""
+    def source_rows_for(self, r0: int, r1: int, halo: int = 0) -> tuple[int, int]:
+        """Global source rows [j0, j1) read by target rows [r0, r1) (clipped);
+        with ``halo`` the windows grow by `halo` rows above and 2 x `halo`
+        below (a floor row on the window's last row reaches floor + 1 + halo)."""
         tys = range(r0 // self.tile_height, (max(r1, r0 + 1) - 1) // self.tile_height + 1)
         ntx = self.num_tiles[0]
         t = np.array([ty * ntx + tx for ty in tys for tx in range(ntx)], dtype=np.int64)
         j0 = int(self.tile_win[t, 1].min())
-        j1 = int(self.tile_win[t, 1].max()) + self.win_height
+        j1 = int(self.tile_win[t, 1].max()) + self.win_height + 2 * halo
+        j0 -= halo
         return max(0, j0), min(self.src_height, max(0, j1))
 
 
@@ -430,7 +450,7 @@ def _reproject_data_array(data_array: DataArray, var_name, target_gm: GridMappin
     data = data_array.data
     on_device = is_device_array(data)
     out_dtype = None
-    if interp_method == "bilinear" and get_options()["reproject_bilinear_dtype"] == "source":
+    if interp_method in ("bilinear", "bicubic") and get_options()["reproject_bilinear_dtype"] == "source":
         out_dtype = data_array.dtype if np.issubdtype(data_array.dtype, np.floating) else np.float64
     expanded = len(data_array.dims) == 2
     devices = multidevice.active_devices()
@@ -471,10 +491,11 @@ def _reproject_partitioned(src, plan: ReprojectPlan, interp: str, fill, out_dtyp
     from .sharding import band_shard
 
     od = np.dtype(out_dtype if out_dtype is not None else
-                  (np.float64 if interp == "bilinear" else _src_dtype(src)))
+                  (np.float64 if interp in ("bilinear", "bicubic") else _src_dtype(src)))
     world = len(devices)
     balance = "cost" if plan.coord_mode == 0 else "rows"
-    shards = [band_shard(plan, world, i, balance, od.itemsize) for i in range(world)]
+    halo = _native.REPROJECT_HALO.get(interp, 0)
+    shards = [band_shard(plan, world, i, balance, od.itemsize, halo) for i in range(world)]
     n = src.shape[0]
     out = multidevice.output_like(src, (n, plan.dst_height, plan.dst_width), od)
 

@@ -154,19 +154,20 @@ def split_predictions(plan, cuts: list[int], out_itemsize: int = 4) -> dict:
 
 
 def band_shard(plan, world: int, rank: int, balance: str = "rows",
-               out_itemsize: int = 4) -> BandShard:
+               out_itemsize: int = 4, halo: int = 0) -> BandShard:
     """Target rows of `rank` in a row-granular split of one raster
     (``band_splits``) and the global source rows they read
     (``ReprojectPlan.source_rows_read``: exactly the rows K1 touches, so a
-    device holds nothing more).  Ranks beyond the number of rows get an
-    empty band."""
+    device holds nothing more; ``halo``: the interpolation method's reach
+    beyond the floor and ceil rows, 1 for bicubic).  Ranks beyond the number
+    of rows get an empty band."""
     if not 0 <= rank < world:
         raise ValueError(f"invalid rank {rank} for world size {world}")
     cuts = band_splits(plan, world, balance, out_itemsize)
     r0, r1 = cuts[rank], cuts[rank + 1]
     if r1 <= r0:
         return BandShard(rank, world, r0, r0, 0, 0)
-    j0, j1 = plan.source_rows_read(r0, r1)
+    j0, j1 = plan.source_rows_read(r0, r1, halo)
     return BandShard(rank, world, r0, r1, j0, j1)
 
 

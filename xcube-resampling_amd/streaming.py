@@ -251,13 +251,13 @@ def band_ranges(height: int, band_rows: int) -> list[tuple[int, int]]:
     return [(r0, min(height, r0 + band_rows)) for r0 in range(0, height, band_rows)]
 
 
-def band_source_rows(plan, bands) -> list[tuple[int, int]]:
+def band_source_rows(plan, bands, halo: int = 0) -> list[tuple[int, int]]:
     """Source rows [j0, j1) each band reads (the union of its tiles' windows,
-    ReprojectPlan.source_rows_for), with j1 made non-decreasing: band b is
-    computed once rows [0, j1_b) are resident."""
+    ReprojectPlan.source_rows_for, widened by the method's ``halo``), with j1
+    made non-decreasing: band b is computed once rows [0, j1_b) are resident."""
     out, hi = [], 0
     for r0, r1 in bands:
-        j0, j1 = plan.source_rows_for(r0, r1)
+        j0, j1 = plan.source_rows_for(r0, r1, halo)
         hi = max(hi, j1)
         out.append((j0, hi))
     return out
@@ -278,12 +278,12 @@ def reproject_host(src: np.ndarray, plan, interp: str, fill: float, out_dtype=No
     if w != plan.src_width or h != plan.src_height:
         raise ValueError(f"source shape {src.shape[1:]} does not match the plan "
                          f"({plan.src_height}, {plan.src_width})")
-    if interp not in _native.INTERP_CODES:
+    if interp not in _native.REPROJECT_INTERP_CODES:
         raise NotImplementedError(
             f"interp_methods must be one of 0, 1, 'nearest', 'bilinear', 'triangular', "
             f"was '{interp}'.")
     if out_dtype is None:
-        out_dtype = np.float64 if interp == "bilinear" else src.dtype
+        out_dtype = np.float64 if interp in ("bilinear", "bicubic") else src.dtype
     out_dtype = np.dtype(out_dtype)
     hd, wd = plan.dst_height, plan.dst_width
     if out is None:
@@ -292,7 +292,7 @@ def reproject_host(src: np.ndarray, plan, interp: str, fill: float, out_dtype=No
         raise ValueError("out must be a C-contiguous (n, H', W') array of the output dtype")
     band_rows = int(band_rows or plan.tile_height)
     bands = band_ranges(hd, band_rows)
-    src_rows = band_source_rows(plan, bands)
+    src_rows = band_source_rows(plan, bands, halo=_native.REPROJECT_HALO.get(interp, 0))
 
     dsrc = empty((n, h, w), src.dtype, device)
     bufs = [empty((n, min(band_rows, hd), wd), out_dtype, device) for _ in range(2)]
@@ -303,7 +303,7 @@ def reproject_host(src: np.ndarray, plan, interp: str, fill: float, out_dtype=No
     # others start: the grid axes when the transformation is fused into the
     # gather (no 2-D coordinate tables: reproject_table_max_bytes holds here
     # too), else the coordinate tables
-    if plan.fused_transform(device):
+    if plan.fused_transform(device, interp):
         plan.device_grid(device)
     else:
         plan.device_tables(device)

@@ -155,11 +155,13 @@ def _get_interp_method_str(interp_methods, key: Hashable, var):
 
 
 def _prep_interp_methods_downscale(interp_methods):
-    """utils.py:239-251."""
-    if interp_methods == "triangular":
+    """utils.py:239-251; the engine's "bicubic" pre-downscales as bilinear too."""
+    if interp_methods in ("triangular", "bicubic"):
         return "bilinear"
-    if isinstance(interp_methods, Mapping) and "triangular" in interp_methods.values():
-        return {k: ("bilinear" if v == "triangular" else v) for k, v in interp_methods.items()}
+    if isinstance(interp_methods, Mapping) and \
+            not {"triangular", "bicubic"}.isdisjoint(interp_methods.values()):
+        return {k: ("bilinear" if v in ("triangular", "bicubic") else v)
+                for k, v in interp_methods.items()}
     return interp_methods
 
 
