@@ -53,7 +53,8 @@ extern "C" {
 #define XRS_INTERP_NEAREST 0
 #define XRS_INTERP_BILINEAR 1
 #define XRS_INTERP_TRIANGULAR 2
-#define XRS_INTERP_BICUBIC 3   /* xrs_reproject only (not the reference's: an engine extension) */
+#define XRS_INTERP_BICUBIC 3   /* xrs_reproject only (not the reference's: an engine extension;
+                                  the affine path has its own entry, xrs_affine_bicubic) */
 
 /* ---- err_flags bits ------------------------------------------------------ */
 #define XRS_EFLAG_INDEX 1     /* numpy IndexError (window index out of range) */
@@ -226,6 +227,43 @@ int xrs_affine(const void* src, int src_dtype, int64_t nt, int64_t src_h, int64_
                int run_weights, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* -------------------------------------------------------------------------
+ * xrs_affine_bicubic — the plain (div = 1) branch of xrs_affine with Keys
+ * cubic convolution, a = -0.5 (an engine extension: the reference refuses
+ * orders above 1 on this path because scipy would blend 3-D arrays across
+ * their leading dimension).  Every (y, x) slice is filtered on its own: no
+ * other slice is read, not even with a zero weight.
+ *
+ * It is sampled at order 1's positions with order 1's inside test.  Per axis
+ * (src, dst, scale, chunk, rel, len, off as for xrs_affine with div 1; the
+ * tables are those of order 1), output index o in chunk k = o / chunk:
+ *   c = off[k] + (double)(o - k*chunk) * scale
+ *   c < 0 or c > len[k] - 1 on either axis: the pixel is cval, cast as
+ *   xrs_affine casts it.  Otherwise f = rel[k] + (int64)floor(c),
+ *   d = c - floor(c), and the taps of the axis are the global source indices
+ *   f-1, f, f+1, f+2, each clamped to [0, size-1] of the whole source axis
+ *   (edge replicate; the chunk's input slice and scipy's mirror play no part).
+ * In float64, without contraction, with w0..w3 in d, the row sums h_j (taps
+ * converted to float64 first) and the column sum exactly as stated for
+ * XRS_INTERP_BICUBIC under xrs_reproject, in that order.  NaN and inf
+ * propagate by the arithmetic.
+ * dst_dtype = src_dtype: the float64 result takes xrs_affine's output cast
+ * (floats rounded once; integers rounded half away from zero and saturated).
+ * No recover_nan (a ratio of two cubic sums with negative lobes is not
+ * defined here) and no coarsen: callers downscale with order 1.
+ * K2q stages each output tile's source rectangle in LDS, filters its rows
+ * into a second LDS array and combines columns from there; launches whose
+ * rectangles exceed the LDS budget (scales well above 1) read the 16 taps
+ * per pixel.  No workspace.  Source axes are limited to INT32_MAX - 4.
+ * ------------------------------------------------------------------------- */
+int xrs_affine_bicubic(const void* src, int src_dtype, int64_t nt, int64_t src_h,
+                       int64_t src_w, int64_t src_st, int64_t src_sy, void* dst, int dst_dtype,
+                       int64_t out_h, int64_t out_w, int64_t dst_st, int64_t dst_sy,
+                       double scale_y, double scale_x, int64_t chunk_y, const int64_t* rel_y,
+                       const int64_t* len_y, const double* off_y, int64_t chunk_x,
+                       const int64_t* rel_x, const int64_t* len_x, const double* off_x,
+                       double cval, void* stream);
+
+/* -------------------------------------------------------------------------
  * xrs_coarsen — replaces da.coarsen(agg, array, {ndim-2: div_y, ndim-1:
  * div_x}) (affine.py:308-310 -> dask chunk.coarsen -> coarsen.py:50-155),
  * SURVEY §8(b) seam 3, for every AGG_METHODS key (constants.py:51-65):
@@ -394,6 +432,11 @@ int xrs_rectify_var(const double* ij, int64_t ij_sn, int64_t dst_h, int64_t dst_
  *   XRS_TESTING_RECTIFY_COMPACT           1 / 2: K5's claim walks every tile's
  *                                         windows compacted across the wave / per
  *                                         lane (0: chosen per tile)
+ *   XRS_TESTING_AFFINE_BICUBIC_DIRECT     1: xrs_affine_bicubic runs the per-pixel
+ *                                         16-tap kernel; 2: the tile kernel with the
+ *                                         smallest staged rectangle (its tiles take
+ *                                         the in-kernel 16-tap path)
+ *   XRS_TESTING_AFFINE_BICUBIC_TILE_H     output rows per K2q tile, 1..64 (0 = 64)
  * Returns the previous value (or XRS_ERR_ARG for an unknown knob).
  * ------------------------------------------------------------------------- */
 #define XRS_TESTING_REPROJECT_BAND 1
@@ -404,7 +447,9 @@ int xrs_rectify_var(const double* ij, int64_t ij_sn, int64_t dst_h, int64_t dst_
 #define XRS_TESTING_RECTIFY_PLAIN_KEYS 7
 #define XRS_TESTING_PROJ_TWO_STEP 8
 #define XRS_TESTING_RECTIFY_COMPACT 9
-#define XRS_TESTING_NUM_KNOBS 10
+#define XRS_TESTING_AFFINE_BICUBIC_DIRECT 10
+#define XRS_TESTING_AFFINE_BICUBIC_TILE_H 11
+#define XRS_TESTING_NUM_KNOBS 12
 int64_t xrs_testing_set(int knob, int64_t value);
 
 /* ---- coordinate transformation (reproject.py:472-496, rectify.py:182-231) --

@@ -1,0 +1,162 @@
+"""Bicubic on the same-CRS affine path (xrs_affine_bicubic, include/xrs.h)
+against a plain numpy float64 restatement, bit for bit: the restatement uses
+no transcendental and the kernel's operation order."""
+
+from __future__ import annotations
+
+import numpy as np
+import pytest
+
+from helpers import assert_bitwise_equal
+
+
+def _axis(n_out, chunk, rel, lens, off, scale, size):
+    """(inside, four clamped global tap indices, four weights) along one axis."""
+    o = np.arange(n_out)
+    k = o // chunk
+    c = off[k] + (o - k * chunk).astype(np.float64) * scale
+    inside = ~((c < 0) | (c > lens[k] - 1))
+    d = c - np.floor(c)
+    f = rel[k] + np.floor(c).astype(np.int64)
+    taps = [np.clip(f - 1 + j, 0, size - 1) for j in range(4)]
+    wts = [((-0.5 * d + 1.0) * d - 0.5) * d, (1.5 * d - 2.5) * (d * d) + 1.0,
+           ((-1.5 * d + 2.0) * d + 0.5) * d, (0.5 * d - 0.5) * (d * d)]
+    return inside, taps, wts
+
+
+def _cast(t, dtype):
+    """scipy's output cast: integers round half away from zero and saturate."""
+    if dtype.kind == "f":
+        return np.asarray(t).astype(dtype)
+    info = np.iinfo(dtype)
+    return np.clip(np.where(t > 0, t + 0.5, t - 0.5), info.min, info.max).astype(dtype)
+
+
+def bicubic_ref(data, plan):
+    """Bicubic of (nt, H, W) `data` at the order-1 positions of `plan`."""
+    _, h, w = data.shape
+    oky, ty, wy = _axis(plan.out_h, plan.chunk_y, plan.rel_y, plan.len_y, plan.off_y,
+                        plan.scale_y, h)
+    okx, tx, wx = _axis(plan.out_w, plan.chunk_x, plan.rel_x, plan.len_x, plan.off_x,
+                        plan.scale_x, w)
+    v = data.astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        hh = [((wx[0] * v[:, r][:, :, tx[0]] + wx[1] * v[:, r][:, :, tx[1]])
+               + wx[2] * v[:, r][:, :, tx[2]]) + wx[3] * v[:, r][:, :, tx[3]] for r in ty]
+        wy = [q[:, None] for q in wy]
+        res = ((wy[0] * hh[0] + wy[1] * hh[1]) + wy[2] * hh[2]) + wy[3] * hh[3]
+    return np.where(oky[:, None] & okx[None, :], _cast(res, data.dtype),
+                    _cast(np.float64(plan.cval), data.dtype))
+
+
+def _plan(shape, dtype, scale, offset, out_hw, chunks, cval=np.nan):
+    from xcube_resampling_amd.affine import plan_affine
+
+    sy, sx = scale if isinstance(scale, tuple) else (scale, scale)
+    matrix = ((sx, 0.0, offset), (0.0, sy, offset))
+    return plan_affine(shape, np.dtype(dtype), matrix, (shape[0],) + out_hw, (shape[0],) + chunks,
+                       "bicubic", "mean", False, cval)
+
+
+def _run(plan, data, knob=None):
+    import torch
+    from xcube_resampling_amd import _native, kernels
+
+    src = torch.from_numpy(data).cuda()
+    if knob is None:
+        return kernels.affine(src, plan).cpu().numpy()
+    with _native.testing_knob(*knob):
+        return kernels.affine(src, plan).cpu().numpy()
+
+
+def test_reference_pins_itself():
+    """d = 0 returns the source; a cubic polynomial is reproduced exactly at
+    interior half-pixel positions (the weights are (-1, 9, 9, -1) / 16: exact
+    for cubics per axis, and every product of these dyadic values is exact)."""
+    data = np.arange(36, dtype=np.float64).reshape(1, 6, 6) ** 2
+    plan = _plan(data.shape, "float64", 1.0, 0.0, (6, 6), (4, 4))
+    assert plan.method == "bicubic" and plan.order == 1 and plan.t_next is None
+    assert_bitwise_equal(bicubic_ref(data, plan), data)
+    cubic = lambda x, y: x * x * x - 2.0 * x * y * y + y   # noqa: E731
+    xx, yy = np.meshgrid(np.arange(6.0), np.arange(6.0))
+    half = bicubic_ref(cubic(xx, yy)[None], _plan(data.shape, "float64", 1.0, 0.5, (6, 6), (4, 4)))
+    assert_bitwise_equal(half[0, 1:4, 1:4], cubic(xx + 0.5, yy + 0.5)[1:4, 1:4])
+    assert np.isnan(half[0, 5]).all() and np.isnan(half[0, :, 5]).all()   # c > len - 1: cval
+
+
+def _data(shape, dtype, seed=5):
+    rng = np.random.default_rng(seed)
+    if np.dtype(dtype).kind in "iu":
+        return (rng.random(shape) * 250).astype(dtype)
+    data = rng.standard_normal(shape).astype(dtype)
+    data[0, 20, 30] = np.nan
+    data[-1, 33, 41] = np.inf
+    return data
+
+
+# (scale, offset, source H x W): x2 upsampling; a negative offset (leading
+# pixels are cval) with the far edge beyond the source too; scale 1
+GEOMETRIES = [(0.5, 0.25, (70, 90)), (0.3, -0.4, (40, 55)), (1.0, 0.37, (70, 90))]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nt", [1, 2])
+@pytest.mark.parametrize("dtype", ["float32", "float64", "int16", "uint8"])
+@pytest.mark.parametrize("scale,offset,shape", GEOMETRIES)
+def test_kernel_against_restatement(scale, offset, shape, dtype, nt):
+    """150 x 200 outputs in dask-image chunks of 64 x 48: several chunks and
+    64-column tiles, remainder tiles, tiles straddling chunk boundaries."""
+    data = _data((nt,) + shape, dtype)
+    cval = -7.4 if dtype == "int16" else 0.0 if dtype == "uint8" else np.nan
+    plan = _plan(data.shape, dtype, scale, offset, (150, 200), (64, 48), cval)
+    ref = bicubic_ref(data, plan)
+    assert_bitwise_equal(_run(plan, data), ref, "K2q")
+    assert_bitwise_equal(_run(plan, data, ("affine_bicubic_direct", 1)), ref, "direct kernel")
+    assert_bitwise_equal(_run(plan, data, ("affine_bicubic_direct", 2)), ref, "in-tile 16 taps")
+    assert_bitwise_equal(_run(plan, data, ("affine_bicubic_tile_h", 24)), ref, "24-row tiles")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("yscale", [3.0, 6.5])
+def test_rectangles_beyond_the_lds_budget(yscale):
+    """y-scale > 1 with x-scale 0.5 stays in the plain branch (affine.py:259);
+    3.0 fits only lower tiles, 6.5 exceeds the budget at every tile height."""
+    data = _data((1, 300, 60), "float32")
+    plan = _plan(data.shape, "float32", (yscale, 0.5), 0.25, (50, 130), (32, 48))
+    assert plan.method == "bicubic" and plan.div_y == 1
+    assert_bitwise_equal(_run(plan, data), bicubic_ref(data, plan))
+
+
+@pytest.mark.gpu
+def test_public_interface():
+    import torch
+    import xcube_resampling_amd as xrs
+    from xcube_resampling_amd import kernels
+    from xcube_resampling_amd.affine import plan_affine
+
+    sgm = xrs.GridMapping.regular((90, 70), (0, 0), 1.0, "EPSG:4326")
+    tgm = xrs.GridMapping.regular((200, 150), (0.1, 0.1), 0.4, "EPSG:4326", tile_size=(48, 64))
+    data = _data((2, 70, 90), "float32")
+    dims = ("t", "lat", "lon")
+    ds = xrs.Dataset(data_vars={"a": (dims, data), "b": (dims, data)},
+                     coords={"lon": ("lon", sgm.x_coords.values), "lat": ("lat", sgm.y_coords.values)})
+    src = torch.from_numpy(data).cuda()
+    plans = {m: plan_affine(data.shape, data.dtype, tgm.ij_transform_to(sgm), (2, 150, 200),
+                            (2, 64, 48), m, "mean", False, np.nan) for m in ("bicubic", 1)}
+    want = {m: kernels.affine(src, p).cpu().numpy() for m, p in plans.items()}
+    assert_bitwise_equal(want["bicubic"], bicubic_ref(data, plans["bicubic"]))
+    out = xrs.resample_in_space(ds, tgm, interp_methods={"a": "bicubic", "b": "bilinear"})
+    assert_bitwise_equal(out["a"].values, want["bicubic"])
+    assert_bitwise_equal(out["b"].values, want[1])
+    two = xrs.affine_transform_dataset(ds, tgm, interp_methods="bicubic", devices=[0, 0])
+    assert_bitwise_equal(two["b"].values, want["bicubic"])
+    coarse = xrs.GridMapping.regular((30, 23), (0, 0), 3.0, "EPSG:4326", tile_size=(16, 16))
+    assert_bitwise_equal(
+        xrs.affine_transform_dataset(ds, coarse, interp_methods="bicubic")["a"].values,
+        xrs.affine_transform_dataset(ds, coarse, interp_methods="bilinear")["a"].values)
+    with pytest.raises(NotImplementedError, match="recover_nans.*bicubic"):
+        xrs.affine_transform_dataset(ds, tgm, interp_methods="bicubic", recover_nans=True)
+    with pytest.raises(KeyError):
+        xrs.affine_transform_dataset(ds, tgm, interp_methods="cubic")
+    with pytest.raises(ValueError, match="interp_methods must be one of"):
+        xrs.affine_transform_dataset(ds, tgm, interp_methods=3)

@@ -54,8 +54,9 @@ XRS_EFLAG_INF_TO_INT = 8
 XRS_EFLAG_STATE = 16
 
 INTERP_CODES = {"nearest": 0, "bilinear": 1, "triangular": 2}
-# xrs_reproject alone also takes bicubic (XRS_INTERP_BICUBIC); rectify and the
-# affine path keep INTERP_CODES and so keep rejecting it
+# xrs_reproject alone also takes bicubic (XRS_INTERP_BICUBIC); rectify keeps
+# INTERP_CODES and so keeps rejecting it, the affine path has an entry point of
+# its own for it (xrs_affine_bicubic)
 REPROJECT_INTERP_CODES = {**INTERP_CODES, "bicubic": 3}
 # source rows beyond the floor / ceil rows a method's taps reach, per side
 # (ReprojectPlan.source_rows_read and friends)
@@ -114,6 +115,14 @@ _SIGNATURES = {
         _c_i64, _c_ptr, _c_ptr, _c_ptr,                                          # y chunks
         _c_i64, _c_ptr, _c_ptr, _c_ptr,                                          # x chunks
         _c_ptr, _c_dbl, _c_int, _c_int, _c_ptr, _c_i64, _c_ptr,                  # t_next .. stream
+    ]),
+    "xrs_affine_bicubic": (_c_int, [
+        _c_ptr, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64,                  # src
+        _c_ptr, _c_int, _c_i64, _c_i64, _c_i64, _c_i64,                          # dst
+        _c_dbl, _c_dbl,                                                          # scale
+        _c_i64, _c_ptr, _c_ptr, _c_ptr,                                          # y chunks
+        _c_i64, _c_ptr, _c_ptr, _c_ptr,                                          # x chunks
+        _c_dbl, _c_ptr,                                                          # cval, stream
     ]),
     "xrs_coarsen_workspace_size": (_c_i64, [_c_i64]),
     "xrs_coarsen": (_c_int, [
@@ -176,7 +185,8 @@ MAX_PROJ_STEPS = 4
 TESTING_KNOBS = {"reproject_band": 1, "reproject_blocks_per_cu": 2, "affine_generic": 3,
                  "rectify_exact": 4, "rectify_margin": 5,
                  "rectify_plain_keys": 7, "proj_two_step": 8,
-                 "rectify_compact": 9}   # 6: retired (K1's column-group deal, round 5)
+                 "rectify_compact": 9,   # 6: retired (K1's column-group deal, round 5)
+                 "affine_bicubic_direct": 10, "affine_bicubic_tile_h": 11}
 
 
 class testing_knob:

@@ -19,6 +19,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _native, kernels, multidevice
+from .constants import INTERP_METHOD_MAPPING
 from .dataset import DataArray, Dataset
 from .device import is_device_array, require_device, to_device
 from . import streaming
@@ -29,7 +30,7 @@ from .utils import (
     _can_apply_affine_transform,
     _get_agg_method,
     _get_fill_value,
-    _get_interp_method_int,
+    _get_interp_method,
     _get_recover_nan,
     _select_variables,
     as_dataset,
@@ -201,6 +202,8 @@ class AffinePlan:
     post_div: tuple[int, int] = (1, 1)
     post_dtype: np.dtype | None = None
     post_chunks: tuple | None = None   # dask chunk ids (t, y, x) for float mode
+    # "bicubic": K2q samples at this (order-1) plan's positions (xrs_affine_bicubic)
+    method: str | None = None
     _cache: dict = field(default_factory=dict, repr=False)
 
     @property
@@ -241,11 +244,27 @@ def _agg_dtype(agg: str, dtype: np.dtype) -> np.dtype:
     return dtype
 
 
-def plan_affine(src_shape, dtype, affine_matrix, output_shape, output_chunks, interp: int,
+def _downscales(affine_matrix, interp) -> bool:
+    """affine.py:253 — note the reference tests affine_matrix[1][0] (not [1][1])."""
+    return bool((affine_matrix[0][0] > 1 or affine_matrix[1][0] > 1) and interp != 0)
+
+
+def plan_affine(src_shape, dtype, affine_matrix, output_shape, output_chunks, interp,
                 agg: str, recover_nan: bool, fill_value) -> AffinePlan:
     """affine.py:243-362 decisions for one (nt, H, W) array (``recover_nan``
-    must already include the reference's ``da.any(mask)`` test)."""
+    must already include the reference's ``da.any(mask)`` test).  ``interp``
+    "bicubic" (engine extension): order 1's plan; in the plain branch it is
+    marked for K2q, in the downscale branch it is the bilinear plan itself."""
     ((i_scale, _, i_off), (_, j_scale, j_off)) = affine_matrix
+    method = None
+    if isinstance(interp, str) and interp == "bicubic":
+        interp = 1
+        if not _downscales(affine_matrix, interp):
+            if recover_nan and np.issubdtype(dtype, np.floating):
+                raise NotImplementedError(
+                    "recover_nans=True is not implemented for interp_methods='bicubic': the "
+                    "ratio of two cubic sums with negative lobes is not defined")
+            method = "bicubic"
     if interp > 1:
         raise ValueError(
             "interp_methods must be one of 0, 1, 'nearest', 'bilinear'. "
@@ -255,8 +274,7 @@ def plan_affine(src_shape, dtype, affine_matrix, output_shape, output_chunks, in
     nt, h, w = src_shape
     out_h, out_w = output_shape[-2], output_shape[-1]
     tile_h, tile_w = output_chunks[-2], output_chunks[-1]
-    # affine.py:253 — note the reference tests affine_matrix[1][0] (not [1][1])
-    if (affine_matrix[0][0] > 1 or affine_matrix[1][0] > 1) and interp != 0:
+    if _downscales(affine_matrix, interp):
         div_y, div_x = math.ceil(abs(j_scale)), math.ceil(abs(i_scale))
         scale_y, scale_x = j_scale / div_y, i_scale / div_x
         agg_name = agg
@@ -286,7 +304,7 @@ def plan_affine(src_shape, dtype, affine_matrix, output_shape, output_chunks, in
     rel_y, len_y, off_y = axis_chunk_params(scale_y, j_off, out_h * div_y, tile_h, h, interp)
     rel_x, len_x, off_x = axis_chunk_params(scale_x, i_off, out_w * div_x, tile_w, w, interp)
     t_next = None
-    if len(output_shape) == 3:
+    if len(output_shape) == 3 and method is None:   # (K2q reads no other slice)
         t_next = time_neighbours(nt, output_chunks[0], interp)
     if post:  # K2 writes the intermediate (out*div, div 1), K7 reduces it
         out_h, out_w, div_y, div_x = out_h * div_y, out_w * div_x, 1, 1
@@ -294,7 +312,7 @@ def plan_affine(src_shape, dtype, affine_matrix, output_shape, output_chunks, in
                       order=interp, scale_y=scale_y, scale_x=scale_x, chunk_y=tile_h,
                       rel_y=rel_y, len_y=len_y, off_y=off_y, chunk_x=tile_w, rel_x=rel_x,
                       len_x=len_x, off_x=off_x, t_next=t_next, cval=float(fill_value),
-                      recover_nan=recover, out_dtype=np.dtype(out_dtype), **post)
+                      recover_nan=recover, out_dtype=np.dtype(out_dtype), method=method, **post)
 
 
 def _resample_array(data, dims, chunks, affine_matrix, output_shape, output_chunks, interp,
@@ -302,6 +320,13 @@ def _resample_array(data, dims, chunks, affine_matrix, output_shape, output_chun
     """Device execution of affine.py:243-362 for one variable."""
     if len(data.shape) > 3:
         raise NotImplementedError("the engine resamples 2-D and 3-D variables")
+    if isinstance(interp, str) and interp == "bicubic":
+        if _downscales(affine_matrix, 1):   # as reproject's pre-downscale: bilinear
+            interp = 1
+        else:   # K2q, resident on one device: the band footprints of the
+                # partitioned and host-streaming paths carry no cubic halo
+            return _resample_bicubic(data, affine_matrix, output_shape, output_chunks, agg,
+                                     recover_nan, fill_value)
     device = require_device()
     devices = multidevice.active_devices()
     if devices is not None:
@@ -336,6 +361,21 @@ def _resample_array(data, dims, chunks, affine_matrix, output_shape, output_chun
     if np.dtype(final_dtype) == np.uint64:
         out = out.cpu().numpy().view(np.uint64)
         return out[0] if expanded else out
+    return out[0] if expanded else out
+
+
+def _resample_bicubic(data, affine_matrix, output_shape, output_chunks, agg, recover_nan,
+                      fill_value):
+    """The plain branch with "bicubic": one K2q launch on the current device."""
+    device = require_device()
+    expanded = len(data.shape) == 2
+    shape = ((1,) if expanded else ()) + tuple(data.shape)
+    dtype = np.dtype(str(data.dtype).replace("torch.", ""))
+    # (recover_nans with a floating dtype raises here, whatever the data holds)
+    plan = plan_affine(shape, dtype, affine_matrix, output_shape, output_chunks, "bicubic", agg,
+                       recover_nan, fill_value)
+    src = host_to_device(data, device)
+    out = kernels.affine(src.unsqueeze(0) if expanded else src, plan)
     return out[0] if expanded else out
 
 
@@ -418,6 +458,15 @@ def resample_dataset(dataset, affine_matrix, yx_dims: tuple[str, str], target_si
                                  interp_methods, agg_methods, recover_nans, fill_values)
 
 
+def _get_interp_method_or_bicubic(interp_methods, key, var):
+    """utils._get_interp_method_int, with the string "bicubic" (and only that
+    spelling) passed through; INTERP_METHOD_MAPPING is the reference's."""
+    m = _get_interp_method(interp_methods, key, var)
+    if isinstance(m, str) and m != "bicubic":
+        m = INTERP_METHOD_MAPPING[m]
+    return m
+
+
 def _resample_dataset(dataset, affine_matrix, yx_dims, target_size, target_tile_size,
                       interp_methods, agg_methods, recover_nans, fill_values) -> Dataset:
     dataset = as_dataset(dataset)
@@ -436,7 +485,7 @@ def _resample_dataset(dataset, affine_matrix, yx_dims, target_size, target_tile_
             res = _resample_array(
                 data_array.data, data_array.dims, data_array.chunks, affine_matrix, output_shape,
                 output_chunks,
-                _get_interp_method_int(interp_methods, var_name, data_array),
+                _get_interp_method_or_bicubic(interp_methods, var_name, data_array),
                 _get_agg_method(agg_methods, var_name, data_array),
                 _get_recover_nan(recover_nans, var_name, data_array),
                 _get_fill_value(fill_values, var_name, data_array))

@@ -36,6 +36,7 @@
 #include <limits>
 #include <type_traits>
 
+#include "xrs_affine.hpp"
 #include "xrs_common.hpp"
 
 namespace xrs {
@@ -49,15 +50,6 @@ struct AxisTab {   // scipy footprint of one intermediate row / column
   int32_t g0;      // global source index of the first tap; -1 = out of bounds (cval)
   int32_t g1;      // second tap (order 1; mirrored); == g0 for order 0
   double w0, w1;   // order-1 spline weights (1 - x, 1 - w0)
-};
-
-struct AxisChunks {
-  int64_t n;             // intermediate length along the axis
-  int64_t chunk;         // dask-image output chunk size (uniform, last may be short)
-  const int64_t* rel;    // per chunk: first index of the input slice
-  const int64_t* len;    // per chunk: input slice length
-  const double* off;     // per chunk: re-based offset (offset + M*chunk_off - rel)
-  double scale;
 };
 
 // scipy map_coordinate, NI_EXTEND_MIRROR (spline footprint of mode "constant")
@@ -75,18 +67,11 @@ __device__ inline int64_t mirror(int64_t idx, int64_t n) {
   return idx;
 }
 
-// o / chunk: a 32-bit division while both fit (the usual case; a 64-bit
-// division is a long software sequence on the critical path of K2)
-__device__ inline int64_t chunk_of(int64_t o, int64_t chunk) {
-  if (((uint64_t)o | (uint64_t)chunk) <= 0x7FFFFFFFull) return (int64_t)((uint32_t)o / (uint32_t)chunk);
-  return o / chunk;
-}
-
 template <int ORDER>
 __device__ inline AxisTab axis_entry(const AxisChunks& a, int64_t o) {
-  const int64_t k = chunk_of(o, a.chunk), ol = o - k * a.chunk;
+  int64_t k;
+  const double c = axis_coord(a, o, k);
   const int64_t n = a.len[k];
-  const double c = a.off[k] + (double)ol * a.scale;
   AxisTab e{-1, -1, 0.0, 0.0};
   if (c < 0.0 || c > (double)(n - 1)) return e;
   if (ORDER == 1) {
@@ -171,25 +156,6 @@ affine_tables_kernel(AxisChunks ay, AxisChunks ax, AxisTab* __restrict__ ytab,
     }
   }
 }
-
-// ---- scipy output casts ----------------------------------------------------
-template <typename T> struct ScipyOut {
-  // integer outputs: round half away from zero, clamp to the type range
-  __device__ static inline T cast(double t) {
-    t = t > 0 ? t + 0.5 : t - 0.5;
-    const double lo = (double)std::numeric_limits<T>::min();
-    const double hi = (double)std::numeric_limits<T>::max();
-    t = t > hi ? hi : t;
-    t = t < lo ? lo : t;
-    return (T)t;
-  }
-};
-template <> struct ScipyOut<float> {
-  __device__ static inline float cast(double t) { return (float)t; }
-};
-template <> struct ScipyOut<double> {
-  __device__ static inline double cast(double t) { return t; }
-};
 
 enum Agg : int {
   AGG_NONE = 0, AGG_MEAN = 1, AGG_SUM = 2, AGG_MAX = 3, AGG_MIN = 4, AGG_PROD = 5,

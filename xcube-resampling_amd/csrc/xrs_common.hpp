@@ -170,6 +170,24 @@ __device__ inline A window_sum(bool whole, int ny, int nx, F&& val2d) {
   return t;
 }
 
+// ---- Keys cubic convolution (K1q, K2q) --------------------------------------
+struct CubicW {
+  double w0, w1, w2, w3;
+};
+// Keys' cubic convolution weights (a = -0.5) of the taps at -1, 0, 1, 2 for the
+// fraction d; the operation order is part of the contract (include/xrs.h)
+__device__ inline CubicW cubic_weights(double d) {
+  CubicW w;
+  w.w0 = ((-0.5 * d + 1.0) * d - 0.5) * d;
+  w.w1 = (1.5 * d - 2.5) * (d * d) + 1.0;
+  w.w2 = ((-1.5 * d + 2.0) * d + 0.5) * d;
+  w.w3 = (0.5 * d - 0.5) * (d * d);
+  return w;
+}
+__device__ inline double cubic_sum(const CubicW& w, double v0, double v1, double v2, double v3) {
+  return ((w.w0 * v0 + w.w1 * v1) + w.w2 * v2) + w.w3 * v3;
+}
+
 __device__ inline void store_any(void* dst, int64_t idx, int dtype, double fv, int64_t iv,
                                  bool is_int) {
   switch (dtype) {

@@ -548,7 +548,8 @@ def any_nan(src, stream=None) -> bool:
 
 def affine(src, plan, out=None, stream=None):
     """K2/K3 — scipy order-0/1 affine resampling per dask-image chunk, fused
-    with the coarsen reducer when ``plan.div`` > 1.
+    with the coarsen reducer when ``plan.div`` > 1; K2q (``xrs_affine_bicubic``)
+    when ``plan.method`` is "bicubic".
 
     src: device tensor (nt, H, W); plan: affine.AffinePlan.
     Returns the device tensor (nt, out_h, out_w) in ``plan.out_dtype``.
@@ -559,13 +560,23 @@ def affine(src, plan, out=None, stream=None):
         out = empty((nt, plan.out_h, plan.out_w), plan.out_dtype, device)
     tabs = plan.device_tables(device)
     lib = _native.lib()
-    ih, iw = plan.out_h * plan.div_y, plan.out_w * plan.div_x
-    nbytes = lib.xrs_affine_workspace_size(ih, iw)
-    ws = _workspace(device, nbytes, stream)
     st, sy, sx = src.stride()
     dt, dy, dx = out.stride()
     if sx != 1 or dx != 1:
         raise ValueError("innermost dimension must be contiguous")
+    if plan.method == "bicubic":   # K2q (plain branch only: plan_affine)
+        code = _native.DTYPE_CODES[_np_dtype(src)]
+        rc = lib.xrs_affine_bicubic(
+            ptr(src), code, nt, h, w, st, sy, ptr(out), _native.dtype_code(plan.out_dtype),
+            plan.out_h, plan.out_w, dt, dy, float(plan.scale_y), float(plan.scale_x),
+            plan.chunk_y, ptr(tabs["rel_y"]), ptr(tabs["len_y"]), ptr(tabs["off_y"]),
+            plan.chunk_x, ptr(tabs["rel_x"]), ptr(tabs["len_x"]), ptr(tabs["off_x"]),
+            float(plan.cval), stream_handle(device, stream))
+        _native.check(rc, "xrs_affine_bicubic")
+        return out
+    ih, iw = plan.out_h * plan.div_y, plan.out_w * plan.div_x
+    nbytes = lib.xrs_affine_workspace_size(ih, iw)
+    ws = _workspace(device, nbytes, stream)
     out_code = _native.dtype_code(np.int64 if np.dtype(plan.out_dtype) == np.uint64
                                   else plan.out_dtype)
     rc = lib.xrs_affine(
