@@ -25,11 +25,19 @@ def _axis(n_out, chunk, rel, lens, off, scale, size):
 
 
 def _cast(t, dtype):
-    """scipy's output cast: integers round half away from zero and saturate."""
+    """scipy's output cast: integers round half away from zero and saturate.
+    int64's upper bound as float64 is 2^63, one past the type: scipy's C cast
+    of the clamped value is x86's integer indefinite, INT64_MIN (pinned against
+    scipy itself in test_dtypes_cpu)."""
+    dtype = np.dtype(dtype)
     if dtype.kind == "f":
         return np.asarray(t).astype(dtype)
     info = np.iinfo(dtype)
-    return np.clip(np.where(t > 0, t + 0.5, t - 0.5), info.min, info.max).astype(dtype)
+    t = np.clip(np.where(t > 0, t + 0.5, t - 0.5), float(info.min), float(info.max))
+    if dtype == np.int64:
+        top = t >= 2.0 ** 63
+        return np.where(top, info.min, np.where(top, 0.0, t).astype(dtype))
+    return t.astype(dtype)
 
 
 def bicubic_ref(data, plan):

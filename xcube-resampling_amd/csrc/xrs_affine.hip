@@ -225,8 +225,7 @@ struct Taps {
       return (I)ScipyOut<T>::cast(cval);
     }
     if (ORDER == 0) {   // scipy's t = 0.0 + v*1.0: the value itself, -0 -> +0
-      const T a = v0[0][0];
-      return (I)(a == (T)0 ? (T)0 : a);
+      return (I)scipy_unit_tap<T>(v0[0][0]);
     }
     if (!RECOVER && ey.w1 == 0.0 && ex.w1 == 0.0) {
       // Integral position (w0 = 1, w1 = 0 on both axes; every integer-factor
@@ -238,9 +237,8 @@ struct Taps {
       if (HAS_T1)
         bad = bad || !is_finite(v1[0][0]) || !is_finite(v1[0][1]) || !is_finite(v1[1][0]) ||
               !is_finite(v1[1][1]);
-      const T a = v0[0][0];
       if (bad) return (I)ScipyOut<T>::cast(NAN);
-      return (I)(a == (T)0 ? (T)0 : a);
+      return (I)scipy_unit_tap<T>(v0[0][0]);
     }
     const double wy[2] = {ey.w0, ey.w1}, wx[2] = {ex.w0, ex.w1};
     double t = 0.0, tn = 0.0;

@@ -45,11 +45,32 @@ template <typename T> struct ScipyOut {
     return (T)t;
   }
 };
+// int64: the clamp's upper bound (double)INT64_MAX is 2^63, one past the type,
+// and scipy's C cast of it on x86 is the integer indefinite INT64_MIN (so is
+// every value that rounds to 2^63 on its way through float64)
+template <> struct ScipyOut<int64_t> {
+  __device__ static inline int64_t cast(double t) {
+    t = t > 0 ? t + 0.5 : t - 0.5;
+    t = t > 9223372036854775808.0 ? 9223372036854775808.0 : t;
+    t = t < -9223372036854775808.0 ? -9223372036854775808.0 : t;
+    return f64_to_i64_x86(t);
+  }
+};
 template <> struct ScipyOut<float> {
   __device__ static inline float cast(double t) { return (float)t; }
 };
 template <> struct ScipyOut<double> {
   __device__ static inline double cast(double t) { return t; }
 };
+
+// scipy's result for a tap of weight one whose other taps add exact zeros
+// (order 0; order 1 at an integral position): t = 0.0 + v, so the value itself
+// with -0 -> +0.  int64 is the one type float64 does not hold exactly: its
+// values pass through float64 and the output cast as in scipy (low bits above
+// 2^53 are lost, values that round to 2^63 come out as INT64_MIN).
+template <typename T> __device__ inline T scipy_unit_tap(T a) { return a == (T)0 ? (T)0 : a; }
+template <> __device__ inline int64_t scipy_unit_tap<int64_t>(int64_t a) {
+  return ScipyOut<int64_t>::cast((double)a);
+}
 
 }  // namespace xrs

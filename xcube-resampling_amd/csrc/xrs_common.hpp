@@ -73,6 +73,15 @@ template <> struct Conv<int64_t> {
   }
 };
 
+// A value picked unchanged by a path that holds it as float64 in the reference
+// (`a.astype(float64)` ... `.astype(a.dtype)`): the identity for every type
+// float64 holds exactly; an int64 loses its low bits beyond 2^53, and one that
+// rounds to 2^63 comes back as INT64_MIN.
+template <typename T> __device__ inline T via_f64(T v) { return v; }
+template <> __device__ inline int64_t via_f64<int64_t>(int64_t v) {
+  return f64_to_i64_x86((double)v);
+}
+
 // ---- XCD-contiguous work mapping -----------------------------------------
 // Blocks are dealt round-robin over the 8 XCDs (blocks b and b+8 share an L2).
 // Each XCD gets one contiguous slice of the row-major work list, walked by its

@@ -1432,7 +1432,9 @@ __device__ inline void sample_px(double fi, double fj, const T* __restrict__ src
   if (INTERP == XRS_INTERP_NEAREST) {
     if (u > 0.5) i0 = min(max(i0 + 1, (int64_t)0), imax);
     if (v > 0.5) j0 = min(max(j0 + 1, (int64_t)0), jmax);
-    for (int64_t s = 0; s < n; ++s) dst[s * dst_sn + p] = src[s * src_sn + j0 * src_sy + i0];
+    // (the reference samples a float64 copy of the variable, rectify.py:630)
+    for (int64_t s = 0; s < n; ++s)
+      dst[s * dst_sn + p] = via_f64<T>(src[s * src_sn + j0 * src_sy + i0]);
     return;
   }
   const int64_t i1 = min(max(i0 + 1, (int64_t)0), imax), j1 = min(max(j0 + 1, (int64_t)0), jmax);
@@ -1557,7 +1559,7 @@ __device__ inline void sample_rows(const double* fi, const double* fj, int nr,
       T out = tfill;
       if (ok[r]) {
         if (INTERP == XRS_INTERP_NEAREST) {
-          out = t00[r];
+          out = via_f64<T>(t00[r]);
         } else {
           const double v00 = (double)t00[r], v01 = (double)t01[r];
           const double v10 = (double)t10[r], v11 = (double)t11[r];
