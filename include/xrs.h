@@ -53,8 +53,10 @@ extern "C" {
 #define XRS_INTERP_NEAREST 0
 #define XRS_INTERP_BILINEAR 1
 #define XRS_INTERP_TRIANGULAR 2
-#define XRS_INTERP_BICUBIC 3   /* xrs_reproject only (not the reference's: an engine extension;
-                                  the affine path has its own entry, xrs_affine_bicubic) */
+#define XRS_INTERP_BICUBIC 3   /* xrs_reproject and xrs_rectify_var (not the reference's: an
+                                  engine extension; the affine path has its own entry,
+                                  xrs_affine_bicubic; xrs_reproject_proj and
+                                  xrs_rectify_ij_var refuse it) */
 
 /* ---- err_flags bits ------------------------------------------------------ */
 #define XRS_EFLAG_INDEX 1     /* numpy IndexError (window index out of range) */
@@ -402,6 +404,32 @@ int xrs_rectify_tiles(const int32_t* acc, int64_t ntiles_x, int64_t ntiles_y, in
  * band's first row, ij_sn = the whole image's plane size); nearest (u > 0.5
  * rounds up), triangular or bilinear in float64, stored in the variable
  * dtype; NaN positions -> fill.  dst: (n, dst_h, dst_w), slice stride dst_sn.
+ *
+ * bicubic (XRS_INTERP_BICUBIC, an engine extension; xrs_rectify_ij_var keeps
+ * refusing it: the fused resolve pass has no bicubic variant): Keys cubic
+ * convolution, a = -0.5, at the same positions with the same classification.
+ * Per target pixel with position (fi, fj): NaN in either coordinate gives
+ * `fill`; a position outside [0, src_w) x [0, src_h) gives `fill`, sets
+ * XRS_EFLAG_STATE and is never dereferenced.  Otherwise i0 = (int32)fi,
+ * j0 = (int32)fj, u = fi - i0, v = fj - j0 as for the other methods, and the
+ * taps of an axis are i0-1, i0, i0+1, i0+2 (j0-1 .. j0+2), each clamped to
+ * [0, size-1] of the whole source axis (edge replicate).  In float64, without
+ * contraction, with w0..w3 in u (x) and in v (y), the four row sums h_j (taps
+ * converted to float64 first, x weights) and then the column sum (y weights)
+ * exactly as stated for XRS_INTERP_BICUBIC under xrs_reproject, in that order.
+ * NaN and inf propagate by the arithmetic (a zero weight masks nothing);
+ * every dim-0 slice is filtered on its own.  The result is stored in the
+ * source dtype: floats rounded once; integers rounded half away from zero
+ * and saturated (xrs_affine_bicubic's cast) — on purpose not the truncating
+ * x86 cast of the other three methods, under which cubic overshoot on a
+ * uint8 edge would wrap (257 -> 1) where it must give 255; `fill` is
+ * converted as for the other methods.  K6q gives a block one tile of target
+ * pixels and all n slices: it stages the tile's source rectangle
+ * [imin-1, imax+2] x [jmin-1, jmax+2] (edge clamp applied) in LDS per slice
+ * and reads the 4 x 4 taps from there; a tile whose rectangle exceeds the LDS
+ * budget (scattered positions, a target far coarser than the swath) reads its
+ * 16 taps per pixel from global memory, same arithmetic.  Source axes are
+ * limited to INT32_MAX - 4 for this method.
  * ------------------------------------------------------------------------- */
 int xrs_rectify_var(const double* ij, int64_t ij_sn, int64_t dst_h, int64_t dst_w, const void* src,
                     int src_dtype, int64_t n, int64_t src_h, int64_t src_w, int64_t src_sn,
@@ -437,6 +465,11 @@ int xrs_rectify_var(const double* ij, int64_t ij_sn, int64_t dst_h, int64_t dst_
  *                                         smallest staged rectangle (its tiles take
  *                                         the in-kernel 16-tap path)
  *   XRS_TESTING_AFFINE_BICUBIC_TILE_H     output rows per K2q tile, 1..64 (0 = 64)
+ *   XRS_TESTING_RECTIFY_BICUBIC_DIRECT    1: every K6q tile reads its 16 taps per
+ *                                         pixel from global memory
+ *   XRS_TESTING_RECTIFY_BICUBIC_LDS       K6q's staging budget in bytes (0 = the
+ *                                         default, at most 48 KiB): a small value
+ *                                         makes a launch mix staged and 16-tap tiles
  * Returns the previous value (or XRS_ERR_ARG for an unknown knob).
  * ------------------------------------------------------------------------- */
 #define XRS_TESTING_REPROJECT_BAND 1
@@ -449,7 +482,9 @@ int xrs_rectify_var(const double* ij, int64_t ij_sn, int64_t dst_h, int64_t dst_
 #define XRS_TESTING_RECTIFY_COMPACT 9
 #define XRS_TESTING_AFFINE_BICUBIC_DIRECT 10
 #define XRS_TESTING_AFFINE_BICUBIC_TILE_H 11
-#define XRS_TESTING_NUM_KNOBS 12
+#define XRS_TESTING_RECTIFY_BICUBIC_DIRECT 12
+#define XRS_TESTING_RECTIFY_BICUBIC_LDS 13
+#define XRS_TESTING_NUM_KNOBS 14
 int64_t xrs_testing_set(int knob, int64_t value);
 
 /* ---- coordinate transformation (reproject.py:472-496, rectify.py:182-231) --

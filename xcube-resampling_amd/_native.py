@@ -54,10 +54,11 @@ XRS_EFLAG_INF_TO_INT = 8
 XRS_EFLAG_STATE = 16
 
 INTERP_CODES = {"nearest": 0, "bilinear": 1, "triangular": 2}
-# xrs_reproject alone also takes bicubic (XRS_INTERP_BICUBIC); rectify keeps
-# INTERP_CODES and so keeps rejecting it, the affine path has an entry point of
-# its own for it (xrs_affine_bicubic)
+# xrs_reproject and xrs_rectify_var also take bicubic (XRS_INTERP_BICUBIC); the
+# fused xrs_rectify_ij_var keeps INTERP_CODES and so keeps rejecting it, the
+# affine path has an entry point of its own for it (xrs_affine_bicubic)
 REPROJECT_INTERP_CODES = {**INTERP_CODES, "bicubic": 3}
+RECTIFY_INTERP_CODES = {**INTERP_CODES, "bicubic": 3}
 # source rows beyond the floor / ceil rows a method's taps reach, per side
 # (ReprojectPlan.source_rows_read and friends)
 REPROJECT_HALO = {"bicubic": 1}
@@ -186,7 +187,8 @@ TESTING_KNOBS = {"reproject_band": 1, "reproject_blocks_per_cu": 2, "affine_gene
                  "rectify_exact": 4, "rectify_margin": 5,
                  "rectify_plain_keys": 7, "proj_two_step": 8,
                  "rectify_compact": 9,   # 6: retired (K1's column-group deal, round 5)
-                 "affine_bicubic_direct": 10, "affine_bicubic_tile_h": 11}
+                 "affine_bicubic_direct": 10, "affine_bicubic_tile_h": 11,
+                 "rectify_bicubic_direct": 12, "rectify_bicubic_lds": 13}
 
 
 class testing_knob:

@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "xrs_common.hpp"
+#include "xrs_rectify.hpp"
 
 namespace xrs {
 namespace {
@@ -2045,8 +2046,9 @@ extern "C" int xrs_rectify_var(const double* ij, int64_t ij_sn, int64_t dst_h, i
                                int interp, double fill, int32_t* err_flags, void* stream) {
   using namespace xrs;
   if (interp != XRS_INTERP_NEAREST && interp != XRS_INTERP_BILINEAR &&
-      interp != XRS_INTERP_TRIANGULAR) {
-    xrs_set_error("interp_methods must be one of 0, 1, 'nearest', 'bilinear', 'triangular'");
+      interp != XRS_INTERP_TRIANGULAR && interp != XRS_INTERP_BICUBIC) {
+    xrs_set_error("interp_methods must be one of 0, 1, 'nearest', 'bilinear', 'triangular', "
+                  "'bicubic'");
     return XRS_ERR_NOTIMPL;
   }
   if (!ij || !src || !dst || !err_flags || dst_h < 1 || dst_w < 1 || n < 1 || src_h < 1 || src_w < 1 ||
@@ -2056,6 +2058,14 @@ extern "C" int xrs_rectify_var(const double* ij, int64_t ij_sn, int64_t dst_h, i
     return XRS_ERR_ARG;
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
+  if (interp == XRS_INTERP_BICUBIC) {   // K6q (the tap indices i0 + 2, j0 + 2 are 32-bit)
+    if (src_h > INT32_MAX - 4 || src_w > INT32_MAX - 4) {
+      xrs_set_error("xrs_rectify_var: bicubic source axes are limited to INT32_MAX - 4");
+      return XRS_ERR_ARG;
+    }
+    return rectify_bicubic_launch(ij, ij_sn, dst_h, dst_w, src, src_dtype, n, src_h, src_w,
+                                  src_sn, src_sy, dst, dst_sn, fill, err_flags, st);
+  }
   const int nb = grid_blocks(dst_h * dst_w, kThreads, 256 * 8);
   return dispatch_dtype(src_dtype, [&](auto tag) -> int {
     using T = decltype(tag);

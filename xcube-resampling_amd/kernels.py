@@ -464,13 +464,14 @@ def rectify_var(ij, src, interp: str, fill, stream=None, rows=None, out=None,
     `ij` (2, H', W') (rectify.py:605-734).  Returns (n, H', W') in src dtype,
     or with ``rows=(r0, r1)`` the target rows [r0, r1) into ``out`` (n, r1-r0,
     W') (default: a new tensor).  Positions outside the source (never made
-    by K5) raise; with a caller's ``flags`` the caller checks them."""
+    by K5) raise; with a caller's ``flags`` the caller checks them.
+    ``interp`` "bicubic" (engine extension) runs K6q."""
     device = src.device
-    code = _native.INTERP_CODES.get(interp)
+    code = _native.RECTIFY_INTERP_CODES.get(interp)
     if code is None:
         raise NotImplementedError(
             f"interp_methods must be one of 0, 1, 'nearest', 'bilinear', "
-            f"'triangular', was '{interp}'.")
+            f"'triangular', 'bicubic', was '{interp}'.")
     n, h, w = src.shape
     _, dh, dw = ij.shape
     r0, r1 = rows if rows is not None else (0, dh)

@@ -14,7 +14,8 @@ target offsets).  The pixel work runs on the device:
                          rectify.py:424-576) — computed once, shared by all
                          variables, and kept in HBM;
 * K6 ``xrs_rectify_var`` per variable, sampling at those positions
-                         (rectify.py:605-734).
+                         (rectify.py:605-734); "bicubic" (engine extension):
+                         K6q, LDS-staged 16-tap sampling, never fused into K5.
 """
 
 from __future__ import annotations
@@ -84,20 +85,26 @@ def _rectify_dataset(source_ds, target_gm, source_gm, variables, interp_methods,
     # 1.45 ms; with 4 rows the bilinear taps cost a wave per SIMD and fusing
     # it was slower, 1.50 vs 1.47 ms)
     devices = multidevice.active_devices()
-    parted, fused = {}, None
+    parted, fused, methods = {}, None, interp_methods
     if devices is not None:   # every variable over the device list (multidevice)
         parted = _rectify_partitioned(source_ds, source_gm, target_gm, rect_vars,
                                       interp_methods, fill_values, devices)
     else:
+        # (the resolve pass has no bicubic variant: a bicubic variable is
+        # sampled by K6q from the kept ij image, and never the fused one)
+        methods = {str(k): _get_interp_method_str(interp_methods, k, source_ds[k])
+                   for k in rect_vars}
         fused = next((k for k in rect_vars if len(source_ds[k].dims) in (2, 3)
-                      and not _streams(source_ds[k].data)), None)
+                      and not _streams(source_ds[k].data)
+                      and methods[str(k)] != "bicubic"), None)
         if fused is not None:
             da = source_ds[fused]
             src = _var_device(da.data)
+            keep_ij = len(rect_vars) > 1 or "bicubic" in methods.values()
             target_source_ij, out = _compute_target_source_ij(
                 source_gm, target_gm, UV_DELTA, var=(
-                    src, _get_interp_method_str(interp_methods, fused, da),
-                    _get_fill_value(fill_values, fused, da), len(rect_vars) > 1))
+                    src, methods[str(fused)], _get_fill_value(fill_values, fused, da),
+                    keep_ij))
             fused_da = _rectified_array(da, target_gm, out)
         else:
             target_source_ij = _compute_target_source_ij(source_gm, target_gm, UV_DELTA)
@@ -122,7 +129,7 @@ def _rectify_dataset(source_ds, target_gm, source_gm, variables, interp_methods,
                 target_ds[var_name] = parted[var_name]
                 continue
             target_ds[var_name] = _rectify_data_array(
-                data_array, var_name, target_gm, target_source_ij, interp_methods, fill_values)
+                data_array, var_name, target_gm, target_source_ij, methods, fill_values)
         elif yx_dims[0] not in data_array.dims and yx_dims[1] not in data_array.dims:
             target_ds[var_name] = data_array
     return target_ds

@@ -436,7 +436,8 @@ def rectify_host(src: np.ndarray, ij, interp: str, fill, device=None,
     result, streamed in target row bands (rectify.py:297-298: numpy in, numpy
     out).  Each band needs the source rows its positions ij read: K6 reads rows
     int(j) and int(j) + 1 (rectify.py:663-734), bounded per target row from ij
-    on the device.  Same values as ``kernels.rectify_var`` on a resident copy."""
+    on the device; "bicubic" (K6q) reads one more row on either side.  Same
+    values as ``kernels.rectify_var`` on a resident copy."""
     t = torch()
     device = require_device(device)
     src = np.ascontiguousarray(src)
@@ -451,13 +452,14 @@ def rectify_host(src: np.ndarray, ij, interp: str, fill, device=None,
     lo, hi = lo.cpu().numpy(), hi.cpu().numpy()
     rows = int(band_rows or _band_rows(hd, n * wd * src.itemsize, 8))
     bands = band_ranges(hd, rows)
+    halo = 1 if interp == "bicubic" else 0
     src_rows = []
     for r0, r1 in bands:
         blo, bhi = lo[r0:r1].min(), hi[r0:r1].max()
         if not np.isfinite(blo):   # nothing to sample: fill only
             src_rows.append((0, 0))
         else:
-            src_rows.append((int(np.floor(blo)), int(np.floor(bhi)) + 2))
+            src_rows.append((int(np.floor(blo)) - halo, int(np.floor(bhi)) + 2 + halo))
     dsrc = empty((n, h, w), src.dtype, device)
     flags = kernels.ErrorFlags(device)
 
