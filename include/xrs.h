@@ -53,10 +53,10 @@ extern "C" {
 #define XRS_INTERP_NEAREST 0
 #define XRS_INTERP_BILINEAR 1
 #define XRS_INTERP_TRIANGULAR 2
-#define XRS_INTERP_BICUBIC 3   /* xrs_reproject and xrs_rectify_var (not the reference's: an
-                                  engine extension; the affine path has its own entry,
-                                  xrs_affine_bicubic; xrs_reproject_proj and
-                                  xrs_rectify_ij_var refuse it) */
+#define XRS_INTERP_BICUBIC 3   /* xrs_reproject, xrs_reproject_proj and xrs_rectify_var (not
+                                  the reference's: an engine extension; the affine path has
+                                  its own entry, xrs_affine_bicubic; xrs_rectify_ij_var
+                                  refuses it) */
 
 /* ---- err_flags bits ------------------------------------------------------ */
 #define XRS_EFLAG_INDEX 1     /* numpy IndexError (window index out of range) */
@@ -141,7 +141,7 @@ int xrs_copy_async(void* dst, const void* src, int64_t bytes, void* stream);
  *   float32 result is the float64 one rounded once.  Separable modes (0, 2)
  *   filter every source row once per work item and column (K1q, a rolling
  *   ring of four h rows); coord_mode 1 reads the 16 taps per pixel.
- *   xrs_reproject_proj does not take this code.
+ *   xrs_reproject_proj takes this code too (K1pq, below).
  *
  * src: (n, src_rows, src_w) with element strides (src_sn, src_sy, 1); row 0
  *      of the buffer is global source row `src_row0` (a device may hold a band).
@@ -470,6 +470,13 @@ int xrs_rectify_var(const double* ij, int64_t ij_sn, int64_t dst_h, int64_t dst_
  *   XRS_TESTING_RECTIFY_BICUBIC_LDS       K6q's staging budget in bytes (0 = the
  *                                         default, at most 48 KiB): a small value
  *                                         makes a launch mix staged and 16-tap tiles
+ *   XRS_TESTING_REPROJECT_PROJ_BICUBIC_DIRECT  1: every K1pq patch reads its 16 taps
+ *                                         per pixel from global memory, whatever
+ *                                         the budget
+ *   XRS_TESTING_REPROJECT_PROJ_BICUBIC_LDS     K1pq's staging budget in bytes, at most
+ *                                         48 KiB (0 = the product's: nothing is
+ *                                         staged, measured faster); a small value
+ *                                         makes a launch mix staged and 16-tap patches
  * Returns the previous value (or XRS_ERR_ARG for an unknown knob).
  * ------------------------------------------------------------------------- */
 #define XRS_TESTING_REPROJECT_BAND 1
@@ -484,7 +491,9 @@ int xrs_rectify_var(const double* ij, int64_t ij_sn, int64_t dst_h, int64_t dst_
 #define XRS_TESTING_AFFINE_BICUBIC_TILE_H 11
 #define XRS_TESTING_RECTIFY_BICUBIC_DIRECT 12
 #define XRS_TESTING_RECTIFY_BICUBIC_LDS 13
-#define XRS_TESTING_NUM_KNOBS 14
+#define XRS_TESTING_REPROJECT_PROJ_BICUBIC_DIRECT 14
+#define XRS_TESTING_REPROJECT_PROJ_BICUBIC_LDS 15
+#define XRS_TESTING_NUM_KNOBS 16
 int64_t xrs_testing_set(int knob, int64_t value);
 
 /* ---- coordinate transformation (reproject.py:472-496, rectify.py:182-231) --
@@ -534,6 +543,18 @@ int xrs_transform(const double* x, const double* y, int64_t w, int64_t h, int gr
  *   the pipeline `steps` (HOST array, as xrs_transform; the same device code,
  *   so the result equals xrs_transform + xrs_reproject(coord_mode 1) bit for
  *   bit).  Every other argument as xrs_reproject; no workspace.
+ * interp: nearest, bilinear, triangular (K1p, one pixel per thread) or
+ *   XRS_INTERP_BICUBIC with dst_dtype float32 or float64 (K1pq): a block owns
+ *   a 32 x 8 patch of target pixels, evaluates the pipeline and bilinear's
+ *   index math once per pixel and filters every pixel's 4 x 4 taps (edge
+ *   replicated) per dim-0 slice with the arithmetic stated under
+ *   xrs_reproject.  The taps come from global memory, or, for a patch whose
+ *   source rectangle [fxmin - 1, fxmax + 2] x [fymin - 1, fymax + 2] fits the
+ *   launch's LDS budget, from that rectangle staged in LDS (the product's
+ *   budget is 0: staging measured slower, see xrs_testing_set).  XRS_EFLAG_BAND is raised per sampled pixel for a
+ *   tap row the band does not hold, never for a staged row no pixel reads.
+ *   The result equals xrs_transform + xrs_reproject(coord_mode 1,
+ *   XRS_INTERP_BICUBIC) bit for bit.
  * ------------------------------------------------------------------------- */
 int xrs_reproject_proj(const void* src, int src_dtype, int64_t n, int64_t src_h,
                        int64_t src_w, int64_t src_row0, int64_t src_rows,

@@ -188,7 +188,8 @@ TESTING_KNOBS = {"reproject_band": 1, "reproject_blocks_per_cu": 2, "affine_gene
                  "rectify_plain_keys": 7, "proj_two_step": 8,
                  "rectify_compact": 9,   # 6: retired (K1's column-group deal, round 5)
                  "affine_bicubic_direct": 10, "affine_bicubic_tile_h": 11,
-                 "rectify_bicubic_direct": 12, "rectify_bicubic_lds": 13}
+                 "rectify_bicubic_direct": 12, "rectify_bicubic_lds": 13,
+                 "reproject_proj_bicubic_direct": 14, "reproject_proj_bicubic_lds": 15}
 
 
 class testing_knob:

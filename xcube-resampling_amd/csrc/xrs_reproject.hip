@@ -383,18 +383,6 @@ __device__ inline void gather_pixel_mode(const GatherArgs& a, int64_t r, int64_t
     gather_pixel<double, double, XRS_INTERP_BILINEAR>(a, r, col, ex, ey);
 }
 
-// n / d for n < 2^31 by a multiply-high (the round-up method: m = floor(2^32
-// (2^l - d) / d) + 1, l = ceil(log2 d); exact for every such n and d >= 1)
-struct DivU32 {
-  uint32_t m, l;
-  static DivU32 make(uint32_t d) {
-    uint32_t l = 0;
-    while ((1ull << l) < d) ++l;
-    return DivU32{(uint32_t)((((1ull << l) - d) << 32) / d + 1), l};
-  }
-  __device__ uint32_t div(uint32_t n) const { return (__umulhi(n, m) + n) >> l; }
-};
-
 template <int K0, int K1, int FAST, int MODE>
 __global__ void __launch_bounds__(kThreads)
 gather_proj_kernel(GatherArgs a, XrsProjStep s0, XrsProjStep s1, int mode, DivU32 div_th,
@@ -627,8 +615,9 @@ extern "C" int xrs_reproject_proj(const void* src, int src_dtype, int64_t n, int
                                   int32_t* err_flags, void* stream) {
   using namespace xrs;
   if (interp != XRS_INTERP_NEAREST && interp != XRS_INTERP_BILINEAR &&
-      interp != XRS_INTERP_TRIANGULAR) {
-    xrs_set_error("interp must be nearest(0), bilinear(1) or triangular(2), was %d", interp);
+      interp != XRS_INTERP_TRIANGULAR && interp != XRS_INTERP_BICUBIC) {
+    xrs_set_error("interp must be nearest(0), bilinear(1), triangular(2) or bicubic(3), was %d",
+                  interp);
     return XRS_ERR_NOTIMPL;
   }
   if (!src || !dst || !grid_x || !grid_y || !tile_x0 || !tile_y0 || !tile_win || !err_flags ||
@@ -651,9 +640,10 @@ extern "C" int xrs_reproject_proj(const void* src, int src_dtype, int64_t n, int
   }
   if (row_begin == row_end) return XRS_OK;
   int variant;
-  if (interp == XRS_INTERP_BILINEAR) {
+  if (interp == XRS_INTERP_BILINEAR || interp == XRS_INTERP_BICUBIC) {
     if (dst_dtype != XRS_DTYPE_F32 && dst_dtype != XRS_DTYPE_F64) {
-      xrs_set_error("xrs_reproject_proj: bilinear output dtype must be float32 or float64");
+      xrs_set_error("xrs_reproject_proj: %s output dtype must be float32 or float64",
+                    interp == XRS_INTERP_BILINEAR ? "bilinear" : "bicubic");
       return XRS_ERR_ARG;
     }
     variant = dst_dtype == XRS_DTYPE_F32 ? 2 : 3;
@@ -686,6 +676,8 @@ extern "C" int xrs_reproject_proj(const void* src, int src_dtype, int64_t n, int
   if (nsteps > 1) s1 = steps[1];
   const int mode = src_dtype * 4 + variant;
   hipStream_t st = static_cast<hipStream_t>(stream);
+  if (interp == XRS_INTERP_BICUBIC)   // K1pq (xrs_reproject_proj_bicubic.hip)
+    return launch_proj_bicubic(a, s0, s1, k0, k1, src_dtype, dst_dtype, st);
   switch (k0) {
     case 0: return launch_proj<0, 0>(a, s0, s1, mode, st);
     case XRS_PROJ_WEBMERC_FWD: return launch_proj<XRS_PROJ_WEBMERC_FWD, 0>(a, s0, s1, mode, st);

@@ -281,11 +281,30 @@ inline Work work_of(const GatherArgs& a, int64_t band = kBand, int64_t segw = kS
   return k;
 }
 
+// n / d for n < 2^31 by a multiply-high (the round-up method: m = floor(2^32
+// (2^l - d) / d) + 1, l = ceil(log2 d); exact for every such n and d >= 1)
+struct DivU32 {
+  uint32_t m, l;
+  static DivU32 make(uint32_t d) {
+    uint32_t l = 0;
+    while ((1ull << l) < d) ++l;
+    return DivU32{(uint32_t)((((1ull << l) - d) << 32) / d + 1), l};
+  }
+  __device__ uint32_t div(uint32_t n) const { return (__umulhi(n, m) + n) >> l; }
+};
+
 // XRS_INTERP_BICUBIC (xrs_reproject_bicubic.hip): K1q for the separable
 // coord_modes, the per-pixel 16-tap gather for coord_mode 1; dst_dtype is
 // float32 or float64 (checked by the caller)
 int launch_bicubic(const GatherArgs& a, int src_dtype, int dst_dtype, int coord_mode,
                    hipStream_t stream);
+
+// XRS_INTERP_BICUBIC under xrs_reproject_proj (xrs_reproject_proj_bicubic.hip):
+// K1pq, the projection per pixel and a patch's source rectangle staged in LDS;
+// the pipeline kinds k0, k1 (0: no step) and dst_dtype (float32 or float64)
+// are checked by the caller
+int launch_proj_bicubic(const GatherArgs& a, const XrsProjStep& s0, const XrsProjStep& s1, int k0,
+                        int k1, int src_dtype, int dst_dtype, hipStream_t stream);
 
 }  // namespace k1
 }  // namespace xrs

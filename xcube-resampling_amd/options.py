@@ -22,8 +22,7 @@
     table traffic overlaps it).  Plans whose tables would exceed this many
     bytes fuse the projection into the gather instead (xrs_reproject_proj: no
     tables, the same values bit for bit).  Default 16 GiB; 0 always fuses.
-    ``interp_methods="bicubic"`` never fuses: the fused gather has no bicubic
-    variant, so such variables go through the tables whatever this option says.
+    Every interpolation method follows this rule ("bicubic" fuses into K1pq).
 
 ``devices``:
     None (default) — every call runs on the current HIP device;

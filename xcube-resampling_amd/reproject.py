@@ -116,10 +116,7 @@ class ReprojectPlan:
         """True when the next K1 call evaluates the transformation per pixel:
         a 2-D plan without coordinate tables on `device` whose tables would
         exceed ``reproject_table_max_bytes`` (or ``fuse_transform`` set).
-        Never for ``interp`` "bicubic": the fused kernel has no bicubic
-        variant, such plans go through coordinate tables whatever their size."""
-        if interp == "bicubic":
-            return False
+        The same rule for every ``interp`` ("bicubic" runs K1pq)."""
         if self.coord_mode != 1 or self.src_x is not None or str(device) in self._device_cache:
             return False
         table_bytes = 16 * self.dst_width * self.dst_height
@@ -417,7 +414,8 @@ def _reproject_dataset(source_ds, target_gm, source_gm, variables, interp_method
     if n_vars == 1 and plan.coord_mode == 1 and plan.src_x is None:
         # one variable over a non-separable pair: the transformation fused into
         # the gather (xrs_reproject_proj) beats tables made for one reader
-        # (config 2u: 1.58 vs 1.63 ms of kernels; bit-identical results)
+        # (config 2u: 1.58 vs 1.63 ms of kernels; bicubic, K1pq: 2.21 vs 3.25 ms,
+        # profiles/proj_bicubic_k1pq.jsonl; bit-identical results)
         import dataclasses
 
         plan = dataclasses.replace(plan, fuse_transform=True)
