@@ -500,7 +500,7 @@ int64_t xrs_testing_set(int knob, int64_t value);
  * xrs_transform — the reference's per-point pyproj transformation for CRS
  *   pairs that are not separable, as a pipeline of up to XRS_MAX_PROJ_STEPS
  *   PROJ operations (source -> geographic -> target: [inverse], [forward] or
- *   [inverse, forward]; degrees for geographic,
+ *   [inverse, forward]; degrees for geographic and rotated-pole CRSs,
  *   metres for projected CRSs, always_xy order).  Each step restates PROJ's
  *   operation as xcube_resampling_amd/projections.py does (results agree with
  *   that numpy restatement to a few ulps: device libm).
@@ -515,15 +515,30 @@ int64_t xrs_testing_set(int knob, int64_t value);
 #define XRS_PROJ_TMERC_INV 4
 #define XRS_PROJ_LAEA_FWD 5      /* laea, ellipsoidal                              */
 #define XRS_PROJ_LAEA_INV 6
+#define XRS_PROJ_STERE_FWD 7     /* stere, ellipsoidal, polar aspects (EPSG:3413, 3031, ...):
+                                    degrees -> metres; rho = akm1 tsfn(phi), the opposite
+                                    pole is +inf                                       */
+#define XRS_PROJ_STERE_INV 8     /* metres -> degrees; the latitude by the conformal ->
+                                    geodetic series (cgb, 6 terms in n), no iteration  */
+#define XRS_PROJ_ROTPOLE_FWD 9   /* geographic degrees -> rotated-pole degrees (CF
+                                    rotated_latitude_longitude, ob_tran o_proj=longlat) */
+#define XRS_PROJ_ROTPOLE_INV 10  /* rotated-pole degrees -> geographic degrees          */
 
 typedef struct XrsProjStep {
   int32_t kind;      /* XRS_PROJ_* */
-  int32_t mode;      /* laea aspect: 0 north pole, 1 south pole, 2 equatorial, 3 oblique */
+  int32_t mode;      /* laea aspect: 0 north pole, 1 south pole, 2 equatorial, 3 oblique;
+                        stere aspect: 0 north pole, 1 south pole */
   double a, ra;      /* semi-major axis, 1 / a */
   double x0, y0;     /* false easting / northing (metres) */
-  double lam0, phi0; /* central meridian / latitude of origin (radians) */
+  double lam0, phi0; /* central meridian / latitude of origin (radians); rotated pole:
+                        lam0 = grid_north_pole_longitude + 180 deg (ob_tran's lon_0) */
   double e, es, one_es;
-  double c[24];      /* tmerc: cgb[6], cbg[6], utg[6], gtu[6] */
+  double c[24];      /* tmerc: cgb[6], cbg[6], utg[6], gtu[6];
+                        stere: c[0] akm1, c[1..6] cgb[6] (only a, ra, x0, y0, lam0, e and
+                        mode are read beside them);
+                        rotated pole: c[0] sin, c[1] cos of grid_north_pole_latitude,
+                        c[2] north_pole_grid_longitude in radians (only lam0 is read
+                        beside them) */
   double Qn, Zb;     /* tmerc */
   double qp, mmf, apa[3], rq, dd, xmf, ymf, sinb1, cosb1;   /* laea */
 } XrsProjStep;

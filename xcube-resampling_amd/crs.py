@@ -8,14 +8,17 @@ the small part of PROJ the engine needs:
 
 * a registry of the CRSs the engine supports (geographic WGS 84 in both axis
   orders, Web Mercator, the UTM zones EPSG:326xx/327xx, LAEA Europe
-  EPSG:3035, and transverse Mercator / LAEA CRSs given by CF parameters), with
+  EPSG:3035, the polar stereographic grids EPSG:3413 / 3031 / 3995 / 3976,
+  transverse Mercator / LAEA / polar stereographic CRSs given by CF
+  parameters, and CF rotated-pole grids), with
   the attributes the reference reads (``is_geographic``, ``name``, ``equals``,
   ``to_cf``, ``axis_info``);
 * ``Transformer`` with ``transform`` and ``transform_bounds`` following PROJ's
   formulas: spherical Mercator (``webmerc``: merc_s_forward / merc_s_inverse
   with ``a = 6378137``; coordinates de-scaled by the reciprocal ``ra = 1/a``;
   radians <-> degrees through a precomputed ``unitconvert`` factor), the
-  ellipsoidal ``tmerc`` and ``laea`` of projections.py, and PROJ's
+  ellipsoidal ``tmerc``, ``laea`` and polar ``stere`` and the rotated pole
+  (``ob_tran`` around ``longlat``) of projections.py, and PROJ's
   ``proj_trans_bounds`` edge densification (21 points per edge by default).
 
 If ``pyproj`` is importable, ``CRS.from_pyproj`` accepts pyproj objects for the
@@ -56,11 +59,13 @@ class CRS:
     authority: str          # "EPSG", "OGC" or "CF" (defined by CF parameters)
     code: str               # "4326", "CRS84", "3857", "32632", "3035", ...
     name: str
-    kind: str               # "geographic" | "webmerc" | "tmerc" | "laea"
+    kind: str               # "geographic" | "webmerc" | "tmerc" | "laea" | "stere" | "rotated"
     axis_order: str         # "latlon" | "lonlat" | "en"
     cf: dict = field(default_factory=dict)
-    # projection parameters (tmerc / laea): ellipsoid name, lon_0, lat_0, k0,
-    # false easting, false northing
+    # projection parameters (tmerc / laea / stere): ellipsoid name, lon_0,
+    # lat_0, k0, false easting, false northing; stere adds lat_ts (None:
+    # variant A, defined by k0); rotated: ellipsoid name, pole latitude, pole
+    # longitude, north_pole_grid_longitude
     params: tuple = ()
 
     # ---- pyproj-like API ------------------------------------------------
@@ -175,7 +180,8 @@ class CRS:
             for crs in list(_REGISTRY.values()) + list(_UTM_CACHE.values()):
                 if crs.cf.get("crs_wkt") == wkt:
                     return crs
-        if gm_name in ("transverse_mercator", "lambert_azimuthal_equal_area"):
+        if gm_name in ("transverse_mercator", "lambert_azimuthal_equal_area",
+                       "polar_stereographic"):
             return _projected_from_cf(attrs)
         if gm_name == "latitude_longitude":
             return _REGISTRY["EPSG:4326"]
@@ -249,6 +255,34 @@ _REGISTRY["EPSG:3035"] = CRS("EPSG", "3035", "ETRS89-extended / LAEA Europe", "l
                              _laea_3035_cf(),
                              ("GRS 1980", 10.0, 52.0, 1.0, 4321000.0, 3210000.0))
 
+
+
+def _polar_stere_crs(code: str, name: str, lat_ts: float, lon_0: float) -> CRS:
+    """A WGS 84 polar stereographic CRS (EPSG method 9829, variant B) with
+    false easting and northing 0."""
+    lat_0 = 90.0 if lat_ts > 0 else -90.0
+    wkt = (f'PROJCRS["{name}",BASEGEOGCRS["WGS 84"],'
+           f'CONVERSION["Polar Stereographic (variant B)"],ID["EPSG",{code}]]')
+    cf = dict(crs_wkt=wkt, semi_major_axis=_WGS84_A, semi_minor_axis=6356752.314245179,
+              inverse_flattening=_WGS84_RF, reference_ellipsoid_name="WGS 84",
+              longitude_of_prime_meridian=0.0, prime_meridian_name="Greenwich",
+              geographic_crs_name="WGS 84",
+              horizontal_datum_name="World Geodetic System 1984 ensemble",
+              projected_crs_name=name, grid_mapping_name="polar_stereographic",
+              standard_parallel=lat_ts, straight_vertical_longitude_from_pole=lon_0,
+              latitude_of_projection_origin=lat_0, false_easting=0.0, false_northing=0.0)
+    return CRS("EPSG", code, name, "stere", "en", cf,
+               ("WGS 84", lon_0, lat_0, 1.0, 0.0, 0.0, lat_ts))
+
+
+for _code, _name, _lat_ts, _lon_0 in (
+        ("3413", "WGS 84 / NSIDC Sea Ice Polar Stereographic North", 70.0, -45.0),
+        ("3031", "WGS 84 / Antarctic Polar Stereographic", -71.0, 0.0),
+        ("3995", "WGS 84 / Arctic Polar Stereographic", 71.0, 0.0),
+        ("3976", "WGS 84 / NSIDC Sea Ice Polar Stereographic South", -70.0, 0.0)):
+    _REGISTRY[f"EPSG:{_code}"] = _polar_stere_crs(_code, _name, _lat_ts, _lon_0)
+_POLAR_CODES = ("3413", "3031", "3995", "3976")
+
 _ALIASES = {
     "EPSG:4326": "EPSG:4326", "WGS84": "EPSG:4326", "4326": "EPSG:4326",
     "OGC:CRS84": "OGC:CRS84", "CRS84": "OGC:CRS84", "OGC:1.3:CRS84": "OGC:CRS84",
@@ -256,6 +290,8 @@ _ALIASES = {
     "EPSG:3857": "EPSG:3857", "3857": "EPSG:3857", "EPSG:900913": "EPSG:3857",
     "EPSG:3035": "EPSG:3035", "3035": "EPSG:3035",
 }
+for _code in _POLAR_CODES:
+    _ALIASES[f"EPSG:{_code}"] = _ALIASES[_code] = f"EPSG:{_code}"
 _UTM_CACHE: dict[int, CRS] = {}
 
 
@@ -287,9 +323,10 @@ def utm_crs(zone: int, south: bool = False) -> CRS:
 
 
 def _projected_from_cf(attrs: dict) -> CRS:
-    """A transverse Mercator / LAEA CRS from its CF grid-mapping parameters
-    (the EPSG definition when the parameters are those of a UTM zone or of
-    EPSG:3035, else a CRS defined by the parameters)."""
+    """A transverse Mercator / LAEA / polar stereographic CRS from its CF
+    grid-mapping parameters (the EPSG definition when the parameters are those
+    of a UTM zone, of EPSG:3035 or of a registered polar grid, else a CRS
+    defined by the parameters)."""
     gm = attrs["grid_mapping_name"]
     rf = float(attrs.get("inverse_flattening", _WGS84_RF))
     ell = "GRS 1980" if abs(rf - 298.257222101) < 1e-9 else "WGS 84"
@@ -306,6 +343,21 @@ def _projected_from_cf(attrs: dict) -> CRS:
         params = (ell, lon_0, lat_0, k0, fe, fn)
         return CRS("CF", "tmerc", attrs.get("projected_crs_name", "Transverse Mercator"),
                    "tmerc", "en", dict(attrs), params)
+    if gm == "polar_stereographic":
+        lon_0 = float(attrs.get("straight_vertical_longitude_from_pole", 0.0))
+        if abs(lat_0) != 90.0:
+            raise ValueError(f"polar_stereographic needs latitude_of_projection_origin "
+                             f"+-90, was {lat_0}")
+        if "standard_parallel" in attrs:   # variant B
+            k0, lat_ts = 1.0, float(attrs["standard_parallel"])
+        else:                              # variant A
+            k0, lat_ts = float(attrs.get("scale_factor_at_projection_origin", 1.0)), None
+        params = (ell, lon_0, lat_0, k0, fe, fn, lat_ts)
+        for code in _POLAR_CODES:
+            if params == _REGISTRY[f"EPSG:{code}"].params:
+                return _REGISTRY[f"EPSG:{code}"]
+        return CRS("CF", "stere", attrs.get("projected_crs_name", "Polar Stereographic"),
+                   "stere", "en", dict(attrs), params)
     lon_0 = float(attrs.get("longitude_of_projection_origin", 0.0))
     params = (ell, lon_0, lat_0, 1.0, fe, fn)
     if params == _REGISTRY["EPSG:3035"].params:
@@ -315,9 +367,9 @@ def _projected_from_cf(attrs: dict) -> CRS:
 
 def rotated_pole_crs(pole_lat: float, pole_lon: float, pole_grid_lon: float = 0.0) -> CRS:
     """A CF rotated latitude-longitude grid (``rotated_latitude_longitude``,
-    PROJ ``ob_tran``): recognised for grid-mapping discovery (cfconv.py:66-212
-    assigns rotated coordinates to it); transformations to or from it raise
-    ``NotImplementedError`` (no rotated-pole grid is on the hot path)."""
+    PROJ ``ob_tran`` around ``longlat``): coordinates are rotated longitude /
+    latitude in degrees; in a Transformer it is one pipeline step like a
+    projected CRS (projections.RotatedPole)."""
     cf = dict(grid_mapping_name="rotated_latitude_longitude",
               grid_north_pole_latitude=pole_lat, grid_north_pole_longitude=pole_lon,
               north_pole_grid_longitude=pole_grid_lon)
@@ -410,14 +462,24 @@ def _projection(crs: CRS):
         return hit
     if crs.kind == "webmerc":
         hit = (webmerc_forward, webmerc_inverse)
+    elif crs.kind == "rotated":
+        from .projections import RotatedPole
+        proj = RotatedPole(*crs.params[1:])
+        hit = (proj.forward, proj.inverse)
     else:
-        from .projections import LambertAzimuthalEqualArea, TransverseMercator
-        ell_name, lon_0, lat_0, k0, x_0, y_0 = crs.params
+        from .projections import (LambertAzimuthalEqualArea, PolarStereographic,
+                                  TransverseMercator)
+        ell_name, lon_0, lat_0, k0, x_0, y_0 = crs.params[:6]
         ell = _ellipsoid(ell_name)
         lam0 = lon_0 * _DEG_TO_RAD
         phi0 = lat_0 * _DEG_TO_RAD
-        proj = (TransverseMercator(ell, k0, phi0) if crs.kind == "tmerc"
-                else LambertAzimuthalEqualArea(ell, phi0))
+        if crs.kind == "stere":
+            lat_ts = crs.params[6]
+            proj = PolarStereographic(ell, phi0, None if lat_ts is None
+                                      else lat_ts * _DEG_TO_RAD, k0)
+        else:
+            proj = (TransverseMercator(ell, k0, phi0) if crs.kind == "tmerc"
+                    else LambertAzimuthalEqualArea(ell, phi0))
         a, ra = ell.a, 1.0 / ell.a
 
         def forward(lon, lat, proj=proj, lam0=lam0, a=a, x_0=x_0, y_0=y_0):
@@ -448,8 +510,16 @@ def _proj_step(crs: CRS, inverse: bool):
         st.kind = PROJ_KINDS["webmerc_inv" if inverse else "webmerc_fwd"]
         st.a, st.ra = _WGS84_A, 1.0 / _WGS84_A
         return st
-    from .projections import LambertAzimuthalEqualArea, TransverseMercator
-    ell_name, lon_0, lat_0, k0, x_0, y_0 = crs.params
+    if crs.kind == "rotated":
+        from .projections import RotatedPole
+        proj = RotatedPole(*crs.params[1:])
+        st.kind = PROJ_KINDS["rotpole_inv" if inverse else "rotpole_fwd"]
+        st.lam0 = proj.lam0
+        st.c[0], st.c[1], st.c[2] = proj.sphip, proj.cphip, proj.lamp
+        return st
+    from .projections import (LambertAzimuthalEqualArea, PolarStereographic,
+                              TransverseMercator)
+    ell_name, lon_0, lat_0, k0, x_0, y_0 = crs.params[:6]
     ell = _ellipsoid(ell_name)
     st.a, st.ra, st.x0, st.y0 = ell.a, 1.0 / ell.a, x_0, y_0
     st.lam0, st.phi0 = lon_0 * _DEG_TO_RAD, lat_0 * _DEG_TO_RAD
@@ -460,6 +530,15 @@ def _proj_step(crs: CRS, inverse: bool):
         for k, v in enumerate(list(proj.cgb) + list(proj.cbg) + list(proj.utg) + list(proj.gtu)):
             st.c[k] = v
         st.Qn, st.Zb = proj.Qn, proj.Zb
+    elif crs.kind == "stere":
+        lat_ts = crs.params[6]
+        proj = PolarStereographic(ell, st.phi0, None if lat_ts is None
+                                  else lat_ts * _DEG_TO_RAD, k0)
+        st.kind = PROJ_KINDS["stere_inv" if inverse else "stere_fwd"]
+        st.mode = 1 if proj.south else 0
+        st.c[0] = proj.akm1
+        for k, v in enumerate(proj.cgb):
+            st.c[1 + k] = v
     else:
         proj = LambertAzimuthalEqualArea(ell, st.phi0)
         st.kind = PROJ_KINDS["laea_inv" if inverse else "laea_fwd"]
@@ -478,7 +557,8 @@ class Transformer:
     """Subset of ``pyproj.Transformer`` used by the reference (always_xy).
 
     Pipelines are source -> geographic -> target; geographic CRSs on WGS 84 and
-    ETRS89 are related by PROJ's null (ballpark) datum transformation."""
+    ETRS89 are related by PROJ's null (ballpark) datum transformation.  A
+    rotated-pole grid takes a step like a projected CRS (its unit is degrees)."""
 
     def __init__(self, crs_from: CRS, crs_to: CRS):
         self.source_crs = crs_from
@@ -489,16 +569,12 @@ class Transformer:
             self._separable = True
             self._step_crs = []
             return
-        if "rotated" in (crs_from.kind, crs_to.kind):
-            raise NotImplementedError(
-                f"transformations to or from a rotated-pole grid are not supported "
-                f"({crs_from!r} -> {crs_to!r})")
         steps = []
         self._step_crs = []   # (crs, inverse) per step: the device pipeline (xrs_transform)
-        if not crs_from.is_geographic:
+        if crs_from.kind != "geographic":
             steps.append(_projection(crs_from)[1])
             self._step_crs.append((crs_from, True))
-        if not crs_to.is_geographic:
+        if crs_to.kind != "geographic":
             steps.append(_projection(crs_to)[0])
             self._step_crs.append((crs_to, False))
 

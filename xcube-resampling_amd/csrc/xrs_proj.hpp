@@ -3,14 +3,17 @@
 // (xrs_reproject_proj).  Each step restates one PROJ operation exactly as
 // xcube_resampling_amd/projections.py + crs.py do in numpy (same formulas, same
 // operation order, -ffp-contract=off): web Mercator (merc_s, webmerc),
-// transverse Mercator (tmerc poder_engsager: Clenshaw gatg / clenS) and
-// Lambert azimuthal equal area (laea e_forward / e_inverse), around PROJ's
-// pj_fwd / pj_inv (lam0 + adjlon, unit-ellipsoid scaling, false origin).
+// transverse Mercator (tmerc poder_engsager: Clenshaw gatg / clenS),
+// Lambert azimuthal equal area (laea e_forward / e_inverse) and polar
+// stereographic (stere e_forward / e_inverse, N_POLE / S_POLE), around PROJ's
+// pj_fwd / pj_inv (lam0 + adjlon, unit-ellipsoid scaling, false origin), and
+// the rotated pole (ob_tran o_forward / o_inverse around longlat).
 // The device libm differs from the host's in the last bit of some
 // transcendentals, so results agree with the numpy restatement to a few ulps.
 #pragma once
 
 #include <cmath>
+#include <type_traits>
 
 #include "xrs_common.hpp"
 
@@ -279,6 +282,88 @@ __device__ inline double adjlon(double lam) {
   return w;
 }
 
+// ---- polar stereographic (projections.py PolarStereographic) -----------------------
+constexpr double kHalfPi = 1.5707963267948966;   // 0.5 * math.pi
+
+// pj_tsfn without pow: tan(pi/4 - phi/2) ((1 + e sin phi) / (1 - e sin phi))^(e/2),
+// the power as exp(e atanh(e sin phi)) through one log, the tangent in the
+// half-angle form of the hemisphere (one division: the operands are selected)
+__device__ inline double tsfn(double sinphi, double cosphi, double e) {
+  const double con = e * sinphi;
+  const bool up = sinphi > 0;
+  const double half = (up ? cosphi : 1.0 - sinphi) / (up ? 1.0 + sinphi : cosphi);
+  return exp(e * (0.5 * log((1.0 + con) / (1.0 - con)))) * half;
+}
+
+// s.c[0]: akm1; s.c[1..6]: cgb; s.mode: kNPole / kSPole
+__device__ inline void stere_fwd(const XrsProjStep& s, double lam, double phi, double& x,
+                                 double& y) {
+  const bool south = s.mode == 1;
+  if (south) phi = -phi;
+  double sinlam, coslam, sinphi, cosphi;
+  sincos(lam, &sinlam, &coslam);
+  sincos(phi, &sinphi, &cosphi);
+  double rho = s.c[0] * tsfn(sinphi, cosphi, s.e);
+  rho = fabs(phi - kHalfPi) < 1e-15 ? 0.0 : rho;
+  rho = phi + kHalfPi < 1.0e-10 ? INFINITY : rho;   // the opposite pole
+  x = rho * sinlam;
+  y = south ? rho * coslam : -rho * coslam;
+}
+
+// PROJ iterates on the latitude with a data-dependent exit; here the conformal
+// latitude chi = pi/2 - 2 atan(t) goes through tmerc's conformal -> geodetic
+// series (gatg, cgb), its double-angle sine and cosine rational in t: one atan
+// and no loop (closer to the exact inverse than 7 fixed iterations)
+__device__ inline void stere_inv(const XrsProjStep& s, double x, double y, double& lam,
+                                 double& phi) {
+  const bool south = s.mode == 1;
+  if (!south) y = -y;
+  // |x|, |y| are a few earth radii at most: no scaling needed
+  const double t = sqrt(x * x + y * y) / s.c[0];
+  const double t2 = t * t;
+  const double den = 1.0 + t2;
+  const double sin_chi = (1.0 - t2) / den;
+  const double cos_chi = (t + t) / den;
+  const double chi = kHalfPi - 2.0 * atan(t);
+  const double sin_2chi = 2.0 * sin_chi * cos_chi;
+  const double cos_2chi = (cos_chi - sin_chi) * (cos_chi + sin_chi);
+  const double ph = gatg(s.c + 1, chi, cos_2chi, sin_2chi);
+  lam = (x == 0.0 && y == 0.0) ? 0.0 : atan2(x, y);
+  phi = south ? -ph : ph;
+}
+
+// ---- rotated pole (projections.py RotatedPole) ---------------------------------------
+// s.c[0], s.c[1]: sin / cos of the pole's latitude; s.c[2]: north_pole_grid_longitude;
+// s.lam0: the pole's longitude + 180 deg.  PROJ aatan2 (0 where both vanish: the
+// arguments are finite or NaN, which atan2_pp serves) and aasin (clip1).
+__device__ inline double aatan2(double n, double d) {
+  return (fabs(n) < 1e-50 && fabs(d) < 1e-50) ? 0.0 : atan2_pp(n, d);
+}
+
+__device__ inline void rotpole_fwd(const XrsProjStep& s, double& x, double& y) {
+  const double lam = adjlon(x * kDegToRad - s.lam0), phi = y * kDegToRad;
+  double sinlam, coslam, sinphi, cosphi;
+  sincos(lam, &sinlam, &coslam);
+  sincos(phi, &sinphi, &cosphi);
+  const double l = adjlon(
+      aatan2(cosphi * sinlam, s.c[0] * cosphi * coslam + s.c[1] * sinphi) + s.c[2]);
+  const double p = asin(clip1(s.c[0] * sinphi - s.c[1] * cosphi * coslam));
+  x = l * (1.0 / kDegToRad);
+  y = p * (1.0 / kDegToRad);
+}
+
+__device__ inline void rotpole_inv(const XrsProjStep& s, double& x, double& y) {
+  const double lam = x * kDegToRad - s.c[2], phi = y * kDegToRad;
+  double sinlam, coslam, sinphi, cosphi;
+  sincos(lam, &sinlam, &coslam);
+  sincos(phi, &sinphi, &cosphi);
+  const double p = asin(clip1(s.c[0] * sinphi + s.c[1] * cosphi * coslam));
+  const double l = adjlon(
+      aatan2(cosphi * sinlam, s.c[0] * cosphi * coslam - s.c[1] * sinphi) + s.lam0);
+  x = l * (1.0 / kDegToRad);
+  y = p * (1.0 / kDegToRad);
+}
+
 // ---- LAEA inverse -> tmerc forward through sines and cosines --------------------
 // The pipeline of a LAEA target grid over a UTM source (config 2u: EPSG:3035 ->
 // EPSG:32632, reproject.py:472-496 per target pixel).  Every intermediate
@@ -403,22 +488,86 @@ __device__ inline void apply_step(const XrsProjStep& s, double& x, double& y) {
     const double phi = atan(sinh(y * s.ra));
     x = lam * rad_to_deg;
     y = phi * rad_to_deg;
-  } else if constexpr (KIND == XRS_PROJ_TMERC_FWD || KIND == XRS_PROJ_LAEA_FWD) {
+  } else if constexpr (KIND == XRS_PROJ_TMERC_FWD || KIND == XRS_PROJ_LAEA_FWD ||
+                       KIND == XRS_PROJ_STERE_FWD) {
     const double lam = adjlon(x * kDegToRad - s.lam0);
     const double phi = y * kDegToRad;
     double px, py;
     if constexpr (KIND == XRS_PROJ_TMERC_FWD) tmerc_fwd(s, lam, phi, px, py);
-    else laea_fwd(s, lam, phi, px, py);
+    else if constexpr (KIND == XRS_PROJ_LAEA_FWD) laea_fwd(s, lam, phi, px, py);
+    else stere_fwd(s, lam, phi, px, py);
     x = s.a * px + s.x0;
     y = s.a * py + s.y0;
-  } else if constexpr (KIND == XRS_PROJ_TMERC_INV || KIND == XRS_PROJ_LAEA_INV) {
+  } else if constexpr (KIND == XRS_PROJ_TMERC_INV || KIND == XRS_PROJ_LAEA_INV ||
+                       KIND == XRS_PROJ_STERE_INV) {
     const double xx = (x - s.x0) * s.ra, yy = (y - s.y0) * s.ra;
     double lam, phi;
     if constexpr (KIND == XRS_PROJ_TMERC_INV) tmerc_inv(s, xx, yy, lam, phi);
-    else laea_inv(s, xx, yy, lam, phi);
+    else if constexpr (KIND == XRS_PROJ_LAEA_INV) laea_inv(s, xx, yy, lam, phi);
+    else stere_inv(s, xx, yy, lam, phi);
     lam = adjlon(lam + s.lam0);
     x = lam * rad_to_deg;
     y = phi * rad_to_deg;
+  } else if constexpr (KIND == XRS_PROJ_ROTPOLE_FWD) {
+    rotpole_fwd(s, x, y);
+  } else if constexpr (KIND == XRS_PROJ_ROTPOLE_INV) {
+    rotpole_inv(s, x, y);
+  }
+}
+
+// ---- the pipelines the launch tables take (host) ----------------------------------
+// XRS_PROJ_* kinds come in pairs: odd forward (to the CRS), even inverse
+inline bool is_valid(int kind) {
+  return kind >= XRS_PROJ_WEBMERC_FWD && kind <= XRS_PROJ_ROTPOLE_INV;
+}
+inline bool is_forward(int kind) { return is_valid(kind) && (kind & 1) != 0; }
+
+// crs.Transformer's shapes: none, [inverse], [forward], [inverse, forward]
+inline bool is_pipeline(int nsteps, int k0, int k1) {
+  if (nsteps == 0) return true;
+  if (!is_valid(k0)) return false;
+  return nsteps == 1 || (nsteps == 2 && !is_forward(k0) && is_forward(k1));
+}
+
+// calls fn(integral_constant<K0>, integral_constant<K1>) for the pipeline (k0, k1)
+// (0: no step), the one table behind xrs_transform, K1p and K1pq
+template <int K0, typename Fn>
+int dispatch_second(int k1, Fn&& fn) {
+  using C0 = std::integral_constant<int, K0>;
+  switch (k1) {
+#define XRS_K1(K) case K: return fn(C0{}, std::integral_constant<int, K>{});
+    XRS_K1(0)
+    XRS_K1(XRS_PROJ_WEBMERC_FWD)
+    XRS_K1(XRS_PROJ_TMERC_FWD)
+    XRS_K1(XRS_PROJ_LAEA_FWD)
+    XRS_K1(XRS_PROJ_STERE_FWD)
+    XRS_K1(XRS_PROJ_ROTPOLE_FWD)
+#undef XRS_K1
+    default: return XRS_ERR_ARG;
+  }
+}
+
+template <typename Fn>
+int dispatch_pipeline(int k0, int k1, Fn&& fn) {
+  using None = std::integral_constant<int, 0>;
+  if (is_forward(k0) && k1 != 0) return XRS_ERR_ARG;
+  switch (k0) {
+#define XRS_K0F(K) case K: return fn(std::integral_constant<int, K>{}, None{});
+#define XRS_K0I(K) case K: return dispatch_second<K>(k1, fn);
+    case 0: return k1 == 0 ? fn(None{}, None{}) : XRS_ERR_ARG;
+    XRS_K0F(XRS_PROJ_WEBMERC_FWD)
+    XRS_K0F(XRS_PROJ_TMERC_FWD)
+    XRS_K0F(XRS_PROJ_LAEA_FWD)
+    XRS_K0F(XRS_PROJ_STERE_FWD)
+    XRS_K0F(XRS_PROJ_ROTPOLE_FWD)
+    XRS_K0I(XRS_PROJ_WEBMERC_INV)
+    XRS_K0I(XRS_PROJ_TMERC_INV)
+    XRS_K0I(XRS_PROJ_LAEA_INV)
+    XRS_K0I(XRS_PROJ_STERE_INV)
+    XRS_K0I(XRS_PROJ_ROTPOLE_INV)
+#undef XRS_K0F
+#undef XRS_K0I
+    default: return XRS_ERR_ARG;
   }
 }
 

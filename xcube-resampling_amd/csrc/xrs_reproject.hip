@@ -454,24 +454,36 @@ int launch(const GatherArgs& a, int coord_mode, hipStream_t stream) {
   return XRS_OK;
 }
 
+// The hot modes get kernels of their own for the pipelines of web Mercator,
+// tmerc and laea, and for the one-step pipelines of stere and the rotated pole
+// (a polar or rotated grid against a geographic one).  A two-step pipeline
+// with stere or the rotated pole in it runs every mode through kModeAny: 20
+// more pipelines x 3 kernels would double this file's build for pairs no
+// workload has shown hot.
+constexpr bool is_new_kind(int k) { return k >= XRS_PROJ_STERE_FWD; }
+template <int K0, int K1>
+constexpr bool kHotModes = !((is_new_kind(K0) || is_new_kind(K1)) && K0 != 0 && K1 != 0);
+
 template <int K0, int K1, int FAST>
 void launch_proj_mode(int nb, const GatherArgs& a, const XrsProjStep& s0, const XrsProjStep& s1,
                       int mode, hipStream_t stream) {
   const DivU32 dh = DivU32::make((uint32_t)a.g.tile_h), dw = DivU32::make((uint32_t)a.g.tile_w);
-  switch (mode) {
+  if constexpr (kHotModes<K0, K1>) {
+    switch (mode) {
 #define XRS_KP(M)                                                                          \
   case M:                                                                                  \
     hipLaunchKernelGGL((gather_proj_kernel<K0, K1, FAST, M>), dim3(nb), dim3(kThreads), 0, \
                        stream, a, s0, s1, mode, dh, dw);                                   \
-    break;
-    XRS_KP(kModeF32Nearest)
-    XRS_KP(kModeF32BilinearF64)
-    XRS_KP(kModeF64BilinearF64)
+    return;
+      XRS_KP(kModeF32Nearest)
+      XRS_KP(kModeF32BilinearF64)
+      XRS_KP(kModeF64BilinearF64)
 #undef XRS_KP
-    default:
-      hipLaunchKernelGGL((gather_proj_kernel<K0, K1, FAST, kModeAny>), dim3(nb), dim3(kThreads),
-                         0, stream, a, s0, s1, mode, dh, dw);
+      default: break;
+    }
   }
+  hipLaunchKernelGGL((gather_proj_kernel<K0, K1, FAST, kModeAny>), dim3(nb), dim3(kThreads), 0,
+                     stream, a, s0, s1, mode, dh, dw);
 }
 
 template <int K0, int K1>
@@ -484,27 +496,18 @@ int launch_proj(const GatherArgs& a, const XrsProjStep& s0, const XrsProjStep& s
   if constexpr (K0 == XRS_PROJ_LAEA_INV && K1 == XRS_PROJ_TMERC_FWD)
     fast = xrs_testing_value(XRS_TESTING_PROJ_TWO_STEP) ? proj::kFastNone
                                                         : proj::fast_kind(K0, K1, s0);
-  if (fast == proj::kFastObliq)
-    launch_proj_mode<K0, K1, proj::kFastObliq>(nb, a, s0, s1, mode, stream);
-  else if (fast == proj::kFastEquit)
-    launch_proj_mode<K0, K1, proj::kFastEquit>(nb, a, s0, s1, mode, stream);
-  else
+  if constexpr (is_new_kind(K0) || is_new_kind(K1)) {   // no fused pair among them
     launch_proj_mode<K0, K1, proj::kFastNone>(nb, a, s0, s1, mode, stream);
+  } else {
+    if (fast == proj::kFastObliq)
+      launch_proj_mode<K0, K1, proj::kFastObliq>(nb, a, s0, s1, mode, stream);
+    else if (fast == proj::kFastEquit)
+      launch_proj_mode<K0, K1, proj::kFastEquit>(nb, a, s0, s1, mode, stream);
+    else
+      launch_proj_mode<K0, K1, proj::kFastNone>(nb, a, s0, s1, mode, stream);
+  }
   XRS_HIP_CHECK(hipGetLastError());
   return XRS_OK;
-}
-
-// pipelines of crs.Transformer: [inverse], [forward], [inverse, forward]
-template <int K0>
-int launch_proj_second(int k1, const GatherArgs& a, const XrsProjStep& s0,
-                       const XrsProjStep& s1, int mode, hipStream_t st) {
-  switch (k1) {
-    case 0: return launch_proj<K0, 0>(a, s0, s1, mode, st);
-    case XRS_PROJ_WEBMERC_FWD: return launch_proj<K0, XRS_PROJ_WEBMERC_FWD>(a, s0, s1, mode, st);
-    case XRS_PROJ_TMERC_FWD: return launch_proj<K0, XRS_PROJ_TMERC_FWD>(a, s0, s1, mode, st);
-    case XRS_PROJ_LAEA_FWD: return launch_proj<K0, XRS_PROJ_LAEA_FWD>(a, s0, s1, mode, st);
-    default: return XRS_ERR_ARG;
-  }
 }
 
 }  // namespace
@@ -630,11 +633,7 @@ extern "C" int xrs_reproject_proj(const void* src, int src_dtype, int64_t n, int
     return XRS_ERR_ARG;
   }
   const int k0 = nsteps > 0 ? steps[0].kind : 0, k1 = nsteps > 1 ? steps[1].kind : 0;
-  const bool fwd0 = k0 == XRS_PROJ_WEBMERC_FWD || k0 == XRS_PROJ_TMERC_FWD ||
-                    k0 == XRS_PROJ_LAEA_FWD;
-  if ((nsteps > 0 && (k0 < XRS_PROJ_WEBMERC_FWD || k0 > XRS_PROJ_LAEA_INV)) ||
-      (nsteps > 1 && (fwd0 || !(k1 == XRS_PROJ_WEBMERC_FWD || k1 == XRS_PROJ_TMERC_FWD ||
-                                k1 == XRS_PROJ_LAEA_FWD)))) {
+  if (!proj::is_pipeline(nsteps, k0, k1)) {
     xrs_set_error("xrs_reproject_proj: unsupported projection pipeline");
     return XRS_ERR_ARG;
   }
@@ -678,16 +677,7 @@ extern "C" int xrs_reproject_proj(const void* src, int src_dtype, int64_t n, int
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (interp == XRS_INTERP_BICUBIC)   // K1pq (xrs_reproject_proj_bicubic.hip)
     return launch_proj_bicubic(a, s0, s1, k0, k1, src_dtype, dst_dtype, st);
-  switch (k0) {
-    case 0: return launch_proj<0, 0>(a, s0, s1, mode, st);
-    case XRS_PROJ_WEBMERC_FWD: return launch_proj<XRS_PROJ_WEBMERC_FWD, 0>(a, s0, s1, mode, st);
-    case XRS_PROJ_TMERC_FWD: return launch_proj<XRS_PROJ_TMERC_FWD, 0>(a, s0, s1, mode, st);
-    case XRS_PROJ_LAEA_FWD: return launch_proj<XRS_PROJ_LAEA_FWD, 0>(a, s0, s1, mode, st);
-    case XRS_PROJ_WEBMERC_INV:
-      return launch_proj_second<XRS_PROJ_WEBMERC_INV>(k1, a, s0, s1, mode, st);
-    case XRS_PROJ_TMERC_INV:
-      return launch_proj_second<XRS_PROJ_TMERC_INV>(k1, a, s0, s1, mode, st);
-    default:
-      return launch_proj_second<XRS_PROJ_LAEA_INV>(k1, a, s0, s1, mode, st);
-  }
+  return proj::dispatch_pipeline(k0, k1, [&](auto c0, auto c1) {
+    return launch_proj<decltype(c0)::value, decltype(c1)::value>(a, s0, s1, mode, st);
+  });
 }

@@ -322,18 +322,6 @@ int launch_pipeline(const Launch& l) {
   return XRS_OK;
 }
 
-// pipelines of crs.Transformer: [inverse], [forward], [inverse, forward]
-template <int K0>
-int launch_second(int k1, const Launch& l) {
-  switch (k1) {
-    case 0: return launch_pipeline<K0, 0>(l);
-    case XRS_PROJ_WEBMERC_FWD: return launch_pipeline<K0, XRS_PROJ_WEBMERC_FWD>(l);
-    case XRS_PROJ_TMERC_FWD: return launch_pipeline<K0, XRS_PROJ_TMERC_FWD>(l);
-    case XRS_PROJ_LAEA_FWD: return launch_pipeline<K0, XRS_PROJ_LAEA_FWD>(l);
-    default: return XRS_ERR_ARG;
-  }
-}
-
 }  // namespace
 
 int k1::launch_proj_bicubic(const GatherArgs& a, const XrsProjStep& s0, const XrsProjStep& s1,
@@ -344,15 +332,9 @@ int k1::launch_proj_bicubic(const GatherArgs& a, const XrsProjStep& s0, const Xr
   const int64_t knob = xrs_testing_value(XRS_TESTING_REPROJECT_PROJ_BICUBIC_LDS);
   const int64_t lds = direct ? 0 : (knob > 0 ? (knob < kLdsMax ? knob : kLdsMax) : kLdsBudget);
   const Launch l{a, s0, s1, src_dtype, dst_dtype == XRS_DTYPE_F32, lds, stream};
-  switch (k0) {
-    case 0: return launch_pipeline<0, 0>(l);
-    case XRS_PROJ_WEBMERC_FWD: return launch_pipeline<XRS_PROJ_WEBMERC_FWD, 0>(l);
-    case XRS_PROJ_TMERC_FWD: return launch_pipeline<XRS_PROJ_TMERC_FWD, 0>(l);
-    case XRS_PROJ_LAEA_FWD: return launch_pipeline<XRS_PROJ_LAEA_FWD, 0>(l);
-    case XRS_PROJ_WEBMERC_INV: return launch_second<XRS_PROJ_WEBMERC_INV>(k1, l);
-    case XRS_PROJ_TMERC_INV: return launch_second<XRS_PROJ_TMERC_INV>(k1, l);
-    default: return launch_second<XRS_PROJ_LAEA_INV>(k1, l);
-  }
+  return proj::dispatch_pipeline(k0, k1, [&](auto c0, auto c1) {
+    return launch_pipeline<decltype(c0)::value, decltype(c1)::value>(l);
+  });
 }
 
 }  // namespace xrs

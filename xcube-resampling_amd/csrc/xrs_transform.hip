@@ -83,23 +83,6 @@ int launch_pipeline(bool grid, int nb, hipStream_t st, const double* x, const do
   return XRS_OK;
 }
 
-// second step: a forward projection (geographic -> target) or none
-template <int K0>
-int launch_second(int k1, bool grid, int nb, hipStream_t st, const double* x, const double* y,
-                  int64_t w, int64_t h, const XrsProjStep& s0, const XrsProjStep& s1,
-                  double* ox, double* oy) {
-  switch (k1) {
-    case 0: return launch_pipeline<K0, 0>(grid, nb, st, x, y, w, h, s0, s1, ox, oy);
-    case XRS_PROJ_WEBMERC_FWD:
-      return launch_pipeline<K0, XRS_PROJ_WEBMERC_FWD>(grid, nb, st, x, y, w, h, s0, s1, ox, oy);
-    case XRS_PROJ_TMERC_FWD:
-      return launch_pipeline<K0, XRS_PROJ_TMERC_FWD>(grid, nb, st, x, y, w, h, s0, s1, ox, oy);
-    case XRS_PROJ_LAEA_FWD:
-      return launch_pipeline<K0, XRS_PROJ_LAEA_FWD>(grid, nb, st, x, y, w, h, s0, s1, ox, oy);
-    default: return XRS_ERR_ARG;
-  }
-}
-
 }  // namespace
 }  // namespace xrs
 
@@ -117,11 +100,7 @@ extern "C" int xrs_transform(const double* x, const double* y, int64_t w, int64_
   const int k0 = nsteps > 0 ? steps[0].kind : 0, k1 = nsteps > 1 ? steps[1].kind : 0;
   if (nsteps > 0) s0 = steps[0];
   if (nsteps > 1) s1 = steps[1];
-  const bool fwd0 = k0 == XRS_PROJ_WEBMERC_FWD || k0 == XRS_PROJ_TMERC_FWD ||
-                    k0 == XRS_PROJ_LAEA_FWD;
-  if ((nsteps > 0 && (k0 < XRS_PROJ_WEBMERC_FWD || k0 > XRS_PROJ_LAEA_INV)) ||
-      (nsteps > 1 && (fwd0 || !(k1 == XRS_PROJ_WEBMERC_FWD || k1 == XRS_PROJ_TMERC_FWD ||
-                                k1 == XRS_PROJ_LAEA_FWD)))) {
+  if (!proj::is_pipeline(nsteps, k0, k1)) {
     xrs_set_error("xrs_transform: unsupported projection pipeline");
     return XRS_ERR_ARG;
   }
@@ -129,28 +108,10 @@ extern "C" int xrs_transform(const double* x, const double* y, int64_t w, int64_
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int nb = grid_blocks(w * h, kThreads, 256 * 16);
   const bool g = grid != 0;
-  int rc;
-  switch (k0) {
-    case 0: rc = launch_pipeline<0, 0>(g, nb, st, x, y, w, h, s0, s1, out_x, out_y); break;
-    case XRS_PROJ_WEBMERC_FWD:
-      rc = launch_pipeline<XRS_PROJ_WEBMERC_FWD, 0>(g, nb, st, x, y, w, h, s0, s1, out_x, out_y);
-      break;
-    case XRS_PROJ_TMERC_FWD:
-      rc = launch_pipeline<XRS_PROJ_TMERC_FWD, 0>(g, nb, st, x, y, w, h, s0, s1, out_x, out_y);
-      break;
-    case XRS_PROJ_LAEA_FWD:
-      rc = launch_pipeline<XRS_PROJ_LAEA_FWD, 0>(g, nb, st, x, y, w, h, s0, s1, out_x, out_y);
-      break;
-    case XRS_PROJ_WEBMERC_INV:
-      rc = launch_second<XRS_PROJ_WEBMERC_INV>(k1, g, nb, st, x, y, w, h, s0, s1, out_x, out_y);
-      break;
-    case XRS_PROJ_TMERC_INV:
-      rc = launch_second<XRS_PROJ_TMERC_INV>(k1, g, nb, st, x, y, w, h, s0, s1, out_x, out_y);
-      break;
-    default:
-      rc = launch_second<XRS_PROJ_LAEA_INV>(k1, g, nb, st, x, y, w, h, s0, s1, out_x, out_y);
-      break;
-  }
+  const int rc = proj::dispatch_pipeline(k0, k1, [&](auto c0, auto c1) {
+    return launch_pipeline<decltype(c0)::value, decltype(c1)::value>(g, nb, st, x, y, w, h, s0,
+                                                                     s1, out_x, out_y);
+  });
   if (rc != XRS_OK) return rc;
   XRS_HIP_CHECK(hipGetLastError());
   return XRS_OK;

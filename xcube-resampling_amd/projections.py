@@ -13,7 +13,11 @@ PROJ's ``pj_fwd`` / ``pj_inv`` do):
   for southern zones);
 * ``LambertAzimuthalEqualArea`` — PROJ ``laea`` ellipsoidal oblique / equatorial
   / polar aspects (``pj_qsfn``, authalic latitude series ``pj_authset`` /
-  ``pj_authlat``).
+  ``pj_authlat``);
+* ``PolarStereographic`` — PROJ ``stere`` in its two polar aspects on the
+  ellipsoid (EPSG methods 9810 variant A: ``k0``, 9829 variant B: ``lat_ts``);
+* ``RotatedPole`` — PROJ ``ob_tran +o_proj=longlat`` as CF's
+  ``rotated_latitude_longitude`` defines it (degrees on both sides).
 
 Parity: PROJ's results are not available here; the restatement is pinned by
 the reference's own PROJ-dependent test goldens (tests/test_reproject.py,
@@ -312,3 +316,116 @@ class LambertAzimuthalEqualArea:
         lam = np.arctan2(x, y)
         phi = self._authlat(np.arcsin(np.clip(ab, -1.0, 1.0)))
         return lam, phi
+
+
+# ---- Polar stereographic (PROJ stere.cpp, N_POLE / S_POLE on the ellipsoid) ------
+_HALFPI = 0.5 * math.pi
+
+
+def _tsfn(sinphi, cosphi, e):
+    """PROJ pj_tsfn without pow: tan(pi/4 - phi/2) ((1 + e sin phi) / (1 - e sin
+    phi))^(e/2), the power as exp(e atanh(e sin phi)) with atanh through one
+    log, the tangent in the half-angle form that keeps its relative accuracy
+    towards the pole."""
+    con = e * sinphi
+    with np.errstate(divide="ignore", invalid="ignore"):
+        half = np.where(sinphi > 0, cosphi / (1.0 + sinphi), (1.0 - sinphi) / cosphi)
+    return np.exp(e * (0.5 * np.log((1.0 + con) / (1.0 - con)))) * half
+
+
+class PolarStereographic:
+    """PROJ stere, ellipsoidal, |lat_0| = 90 deg (e_forward / e_inverse, N_POLE
+    and S_POLE).  ``phits`` (variant B, radians) or, when it is None, ``k0``
+    (variant A).  The inverse is the conformal -> geodetic latitude series
+    (tmerc's ``cgb`` through ``_gatg``) applied to chi = pi/2 - 2 atan(t), whose
+    sine and cosine are rational in t, instead of PROJ's data-dependent
+    iteration."""
+
+    def __init__(self, ell: Ellipsoid, phi0: float, phits: float | None, k0: float = 1.0):
+        if abs(abs(phi0) - _HALFPI) >= _EPS10:
+            raise ValueError("PolarStereographic needs lat_0 = +-90 degrees")
+        self.ell = ell
+        self.south = phi0 < 0
+        e = ell.e
+        phits = _HALFPI if phits is None else abs(phits)
+        if abs(phits - _HALFPI) < _EPS10:
+            self.akm1 = 2.0 * k0 / math.sqrt(math.pow(1 + e, 1 + e) * math.pow(1 - e, 1 - e))
+        else:
+            t = math.sin(phits)
+            self.akm1 = (math.cos(phits) / float(_tsfn(t, math.cos(phits), e))
+                         / math.sqrt(1.0 - (e * t) * (e * t)))
+        self.cgb = TransverseMercator(ell, 1.0).cgb
+
+    def forward(self, lam, phi):
+        lam = np.asarray(lam, dtype=np.float64)
+        phi = np.asarray(phi, dtype=np.float64)
+        if self.south:
+            phi = -phi
+        sinlam, coslam = np.sin(lam), np.cos(lam)
+        sinphi, cosphi = np.sin(phi), np.cos(phi)
+        rho = self.akm1 * _tsfn(sinphi, cosphi, self.ell.e)
+        rho = np.where(np.abs(phi - _HALFPI) < 1e-15, 0.0, rho)
+        rho = np.where(phi + _HALFPI < _EPS10, np.inf, rho)   # the opposite pole
+        x = rho * sinlam
+        y = rho * coslam if self.south else -rho * coslam
+        return x, y
+
+    def inverse(self, x, y):
+        x = np.asarray(x, dtype=np.float64)
+        y = np.asarray(y, dtype=np.float64)
+        if not self.south:
+            y = -y
+        t = np.sqrt(x * x + y * y) / self.akm1   # a few earth radii at most: no scaling
+        t2 = t * t
+        den = 1.0 + t2
+        with np.errstate(invalid="ignore"):
+            sin_chi = (1.0 - t2) / den
+            cos_chi = (t + t) / den
+        chi = _HALFPI - 2.0 * np.arctan(t)
+        sin_2chi = 2.0 * sin_chi * cos_chi
+        cos_2chi = (cos_chi - sin_chi) * (cos_chi + sin_chi)
+        phi = _gatg(self.cgb, chi, cos_2chi, sin_2chi)
+        lam = np.where((x == 0.0) & (y == 0.0), 0.0, np.arctan2(x, y))
+        return lam, (-phi if self.south else phi)
+
+
+# ---- Rotated pole (PROJ ob_tran.cpp o_forward / o_inverse around longlat) ----------
+def _aatan2(n, d):
+    """PROJ aatan2: 0 where both arguments vanish."""
+    return np.where((np.abs(n) < 1e-50) & (np.abs(d) < 1e-50), 0.0, np.arctan2(n, d))
+
+
+class RotatedPole:
+    """CF ``rotated_latitude_longitude``: PROJ ``+proj=ob_tran +o_proj=longlat
+    +o_lat_p=pole_lat +o_lon_p=pole_grid_lon +lon_0=pole_lon + 180``.  A
+    spherical rotation of (lon, lat); ``forward`` takes geographic degrees to
+    rotated degrees, ``inverse`` the other way."""
+
+    def __init__(self, pole_lat: float, pole_lon: float, pole_grid_lon: float = 0.0):
+        from .crs import _DEG_TO_RAD
+        self.lam0 = ((pole_lon + 360.0) % 360.0 - 180.0) * _DEG_TO_RAD   # lon_0, in [-180, 180)
+        self.lamp = pole_grid_lon * _DEG_TO_RAD
+        phip = pole_lat * _DEG_TO_RAD
+        self.sphip, self.cphip = math.sin(phip), math.cos(phip)
+
+    def forward(self, lon, lat):
+        from .crs import _DEG_TO_RAD, _RAD_TO_DEG_FACTOR, _adjlon
+        lam = _adjlon(np.asarray(lon, dtype=np.float64) * _DEG_TO_RAD - self.lam0)
+        phi = np.asarray(lat, dtype=np.float64) * _DEG_TO_RAD
+        sinlam, coslam = np.sin(lam), np.cos(lam)
+        sinphi, cosphi = np.sin(phi), np.cos(phi)
+        lam = _adjlon(_aatan2(cosphi * sinlam, self.sphip * cosphi * coslam + self.cphip * sinphi)
+                      + self.lamp)
+        phi = np.arcsin(np.clip(self.sphip * sinphi - self.cphip * cosphi * coslam, -1.0, 1.0))
+        return lam * _RAD_TO_DEG_FACTOR, phi * _RAD_TO_DEG_FACTOR
+
+    def inverse(self, rlon, rlat):
+        from .crs import _DEG_TO_RAD, _RAD_TO_DEG_FACTOR, _adjlon
+        lam = np.asarray(rlon, dtype=np.float64) * _DEG_TO_RAD - self.lamp
+        phi = np.asarray(rlat, dtype=np.float64) * _DEG_TO_RAD
+        sinlam, coslam = np.sin(lam), np.cos(lam)
+        sinphi, cosphi = np.sin(phi), np.cos(phi)
+        phi = np.arcsin(np.clip(self.sphip * sinphi + self.cphip * cosphi * coslam, -1.0, 1.0))
+        lam = _aatan2(cosphi * sinlam, self.sphip * cosphi * coslam - self.cphip * sinphi)
+        lam = _adjlon(lam + self.lam0)
+        return lam * _RAD_TO_DEG_FACTOR, phi * _RAD_TO_DEG_FACTOR
