@@ -523,11 +523,22 @@ int64_t xrs_testing_set(int knob, int64_t value);
 #define XRS_PROJ_ROTPOLE_FWD 9   /* geographic degrees -> rotated-pole degrees (CF
                                     rotated_latitude_longitude, ob_tran o_proj=longlat) */
 #define XRS_PROJ_ROTPOLE_INV 10  /* rotated-pole degrees -> geographic degrees          */
+#define XRS_PROJ_LCC_FWD 11      /* lcc, ellipsoidal, 1SP / 2SP (EPSG:3034, 2154, CF
+                                    lambert_conformal_conic): degrees -> metres; rho =
+                                    c tsfn(phi)^n, 0 at the apex pole, +inf at the other */
+#define XRS_PROJ_LCC_INV 12      /* metres -> degrees; ts = (rho / c)^(1/n), the latitude
+                                    by the series of XRS_PROJ_STERE_INV, no iteration   */
+#define XRS_PROJ_GEOS_FWD 13     /* geos, ellipsoidal (CF geostationary): degrees ->
+                                    scan angle x perspective point height in metres;
+                                    both outputs +inf where the satellite does not see
+                                    the point                                          */
+#define XRS_PROJ_GEOS_INV 14     /* metres -> degrees; both outputs +inf off the disc   */
 
 typedef struct XrsProjStep {
   int32_t kind;      /* XRS_PROJ_* */
   int32_t mode;      /* laea aspect: 0 north pole, 1 south pole, 2 equatorial, 3 oblique;
-                        stere aspect: 0 north pole, 1 south pole */
+                        stere aspect: 0 north pole, 1 south pole;
+                        geos sweep axis: 0 y (Meteosat, Himawari), 1 x (GOES) */
   double a, ra;      /* semi-major axis, 1 / a */
   double x0, y0;     /* false easting / northing (metres) */
   double lam0, phi0; /* central meridian / latitude of origin (radians); rotated pole:
@@ -538,7 +549,12 @@ typedef struct XrsProjStep {
                         mode are read beside them);
                         rotated pole: c[0] sin, c[1] cos of grid_north_pole_latitude,
                         c[2] north_pole_grid_longitude in radians (only lam0 is read
-                        beside them) */
+                        beside them);
+                        lcc: c[0] n, c[1] c, c[2] rho0, c[3] k0, c[4..9] cgb[6] (only a, ra,
+                        x0, y0, lam0 and e are read beside them);
+                        geos: c[0] radius_g = 1 + h / a, c[1] radius_g_1 = h / a, c[2]
+                        radius_g^2 - 1, c[3] sqrt(1 - es), c[4] 1 / (1 - es) (only a, ra,
+                        x0, y0, lam0, one_es and mode are read beside them) */
   double Qn, Zb;     /* tmerc */
   double qp, mmf, apa[3], rq, dd, xmf, ymf, sinb1, cosb1;   /* laea */
 } XrsProjStep;

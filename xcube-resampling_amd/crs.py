@@ -9,16 +9,17 @@ the small part of PROJ the engine needs:
 * a registry of the CRSs the engine supports (geographic WGS 84 in both axis
   orders, Web Mercator, the UTM zones EPSG:326xx/327xx, LAEA Europe
   EPSG:3035, the polar stereographic grids EPSG:3413 / 3031 / 3995 / 3976,
-  transverse Mercator / LAEA / polar stereographic CRSs given by CF
-  parameters, and CF rotated-pole grids), with
+  the Lambert conformal conic grids EPSG:3034 / 2154, transverse Mercator /
+  LAEA / polar stereographic / Lambert conformal conic / geostationary CRSs
+  given by CF parameters, and CF rotated-pole grids), with
   the attributes the reference reads (``is_geographic``, ``name``, ``equals``,
   ``to_cf``, ``axis_info``);
 * ``Transformer`` with ``transform`` and ``transform_bounds`` following PROJ's
   formulas: spherical Mercator (``webmerc``: merc_s_forward / merc_s_inverse
   with ``a = 6378137``; coordinates de-scaled by the reciprocal ``ra = 1/a``;
   radians <-> degrees through a precomputed ``unitconvert`` factor), the
-  ellipsoidal ``tmerc``, ``laea`` and polar ``stere`` and the rotated pole
-  (``ob_tran`` around ``longlat``) of projections.py, and PROJ's
+  ellipsoidal ``tmerc``, ``laea``, polar ``stere``, ``lcc`` and ``geos`` and the
+  rotated pole (``ob_tran`` around ``longlat``) of projections.py, and PROJ's
   ``proj_trans_bounds`` edge densification (21 points per edge by default).
 
 If ``pyproj`` is importable, ``CRS.from_pyproj`` accepts pyproj objects for the
@@ -59,13 +60,16 @@ class CRS:
     authority: str          # "EPSG", "OGC" or "CF" (defined by CF parameters)
     code: str               # "4326", "CRS84", "3857", "32632", "3035", ...
     name: str
-    kind: str               # "geographic" | "webmerc" | "tmerc" | "laea" | "stere" | "rotated"
+    # "geographic" | "webmerc" | "tmerc" | "laea" | "stere" | "lcc" | "geos" | "rotated"
+    kind: str
     axis_order: str         # "latlon" | "lonlat" | "en"
     cf: dict = field(default_factory=dict)
     # projection parameters (tmerc / laea / stere): ellipsoid name, lon_0,
     # lat_0, k0, false easting, false northing; stere adds lat_ts (None:
     # variant A, defined by k0); rotated: ellipsoid name, pole latitude, pole
-    # longitude, north_pole_grid_longitude
+    # longitude, north_pole_grid_longitude; lcc adds lat_1, lat_2; geos adds the
+    # perspective point height, the sweep axis and its ellipsoid's a and rf (the
+    # ellipsoid name is "custom" unless they are WGS 84's or GRS 1980's)
     params: tuple = ()
 
     # ---- pyproj-like API ------------------------------------------------
@@ -181,8 +185,10 @@ class CRS:
                 if crs.cf.get("crs_wkt") == wkt:
                     return crs
         if gm_name in ("transverse_mercator", "lambert_azimuthal_equal_area",
-                       "polar_stereographic"):
+                       "polar_stereographic", "lambert_conformal_conic"):
             return _projected_from_cf(attrs)
+        if gm_name == "geostationary":
+            return _geostationary_from_cf(attrs)
         if gm_name == "latitude_longitude":
             return _REGISTRY["EPSG:4326"]
         if gm_name == "rotated_latitude_longitude":
@@ -283,6 +289,31 @@ for _code, _name, _lat_ts, _lon_0 in (
     _REGISTRY[f"EPSG:{_code}"] = _polar_stere_crs(_code, _name, _lat_ts, _lon_0)
 _POLAR_CODES = ("3413", "3031", "3995", "3976")
 
+def _lcc_crs(code: str, name: str, conversion: str, lat_1: float, lat_2: float, lat_0: float,
+             lon_0: float, fe: float, fn: float, geo: str, datum: str) -> CRS:
+    """A GRS 1980 Lambert conformal conic CRS with two standard parallels (EPSG
+    method 9802)."""
+    wkt = (f'PROJCRS["{name}",BASEGEOGCRS["{geo}"],CONVERSION["{conversion}"],'
+           f'ID["EPSG",{code}]]')
+    cf = dict(crs_wkt=wkt, semi_major_axis=_WGS84_A, semi_minor_axis=_GRS80_B,
+              inverse_flattening=298.257222101, reference_ellipsoid_name="GRS 1980",
+              longitude_of_prime_meridian=0.0, prime_meridian_name="Greenwich",
+              geographic_crs_name=geo, horizontal_datum_name=datum,
+              projected_crs_name=name, grid_mapping_name="lambert_conformal_conic",
+              standard_parallel=(lat_1, lat_2), latitude_of_projection_origin=lat_0,
+              longitude_of_central_meridian=lon_0, false_easting=fe, false_northing=fn)
+    return CRS("EPSG", code, name, "lcc", "en", cf,
+               ("GRS 1980", lon_0, lat_0, 1.0, fe, fn, lat_1, lat_2))
+
+
+_REGISTRY["EPSG:3034"] = _lcc_crs(
+    "3034", "ETRS89-extended / LCC Europe", "Europe Conformal 2001", 35.0, 65.0, 52.0, 10.0,
+    4000000.0, 2800000.0, "ETRS89", "European Terrestrial Reference System 1989 ensemble")
+_REGISTRY["EPSG:2154"] = _lcc_crs(
+    "2154", "RGF93 v1 / Lambert-93", "Lambert-93", 49.0, 44.0, 46.5, 3.0,
+    700000.0, 6600000.0, "RGF93 v1", "Reseau Geodesique Francais 1993 v1")
+_LCC_CODES = ("3034", "2154")
+
 _ALIASES = {
     "EPSG:4326": "EPSG:4326", "WGS84": "EPSG:4326", "4326": "EPSG:4326",
     "OGC:CRS84": "OGC:CRS84", "CRS84": "OGC:CRS84", "OGC:1.3:CRS84": "OGC:CRS84",
@@ -290,7 +321,7 @@ _ALIASES = {
     "EPSG:3857": "EPSG:3857", "3857": "EPSG:3857", "EPSG:900913": "EPSG:3857",
     "EPSG:3035": "EPSG:3035", "3035": "EPSG:3035",
 }
-for _code in _POLAR_CODES:
+for _code in _POLAR_CODES + _LCC_CODES:
     _ALIASES[f"EPSG:{_code}"] = _ALIASES[_code] = f"EPSG:{_code}"
 _UTM_CACHE: dict[int, CRS] = {}
 
@@ -323,10 +354,10 @@ def utm_crs(zone: int, south: bool = False) -> CRS:
 
 
 def _projected_from_cf(attrs: dict) -> CRS:
-    """A transverse Mercator / LAEA / polar stereographic CRS from its CF
-    grid-mapping parameters (the EPSG definition when the parameters are those
-    of a UTM zone, of EPSG:3035 or of a registered polar grid, else a CRS
-    defined by the parameters)."""
+    """A transverse Mercator / LAEA / polar stereographic / Lambert conformal
+    conic CRS from its CF grid-mapping parameters (the EPSG definition when the
+    parameters are those of a UTM zone, of EPSG:3035 or of a registered polar
+    or conic grid, else a CRS defined by the parameters)."""
     gm = attrs["grid_mapping_name"]
     rf = float(attrs.get("inverse_flattening", _WGS84_RF))
     ell = "GRS 1980" if abs(rf - 298.257222101) < 1e-9 else "WGS 84"
@@ -358,12 +389,69 @@ def _projected_from_cf(attrs: dict) -> CRS:
                 return _REGISTRY[f"EPSG:{code}"]
         return CRS("CF", "stere", attrs.get("projected_crs_name", "Polar Stereographic"),
                    "stere", "en", dict(attrs), params)
+    if gm == "lambert_conformal_conic":
+        lon_0 = float(attrs.get("longitude_of_central_meridian", 0.0))
+        sp = np.atleast_1d(np.asarray(attrs["standard_parallel"], dtype=np.float64))
+        if sp.size not in (1, 2):
+            raise ValueError(f"lambert_conformal_conic needs one or two standard parallels, "
+                             f"was {attrs['standard_parallel']!r}")
+        lat_1, lat_2 = float(sp[0]), float(sp[-1])
+        if "latitude_of_projection_origin" not in attrs:
+            lat_0 = lat_1   # PROJ: lat_0 defaults to lat_1
+        params = (ell, lon_0, lat_0, 1.0, fe, fn, lat_1, lat_2)
+        for code in _LCC_CODES:
+            if params == _REGISTRY[f"EPSG:{code}"].params:
+                return _REGISTRY[f"EPSG:{code}"]
+        return CRS("CF", "lcc", attrs.get("projected_crs_name", "Lambert Conformal Conic"),
+                   "lcc", "en", dict(attrs), params)
     lon_0 = float(attrs.get("longitude_of_projection_origin", 0.0))
     params = (ell, lon_0, lat_0, 1.0, fe, fn)
     if params == _REGISTRY["EPSG:3035"].params:
         return _REGISTRY["EPSG:3035"]
     return CRS("CF", "laea", attrs.get("projected_crs_name", "Lambert Azimuthal Equal Area"),
                "laea", "en", dict(attrs), params)
+
+
+def geostationary_crs(lon_0: float, height: float = 35786023.0, sweep: str = "y",
+                      a: float = _WGS84_A, rf: float = _WGS84_RF, false_easting: float = 0.0,
+                      false_northing: float = 0.0) -> CRS:
+    """A CF ``geostationary`` grid (PROJ ``geos``): the view from ``height``
+    metres above the ellipsoid over longitude ``lon_0``, ``sweep`` "y"
+    (Meteosat, Himawari; PROJ's default) or "x" (GOES).  Coordinates are PROJ's:
+    the scan angle in radians times ``height``, in metres (CF files that store
+    the angle itself are scaled by the caller, as with pyproj)."""
+    if sweep not in ("x", "y"):
+        raise ValueError(f"geostationary sweep axis must be 'x' or 'y', was {sweep!r}")
+    ell = {(_WGS84_A, _WGS84_RF): "WGS 84", (_WGS84_A, 298.257222101): "GRS 1980"}.get(
+        (a, rf), "custom")
+    cf = dict(grid_mapping_name="geostationary", perspective_point_height=height,
+              longitude_of_projection_origin=lon_0, latitude_of_projection_origin=0.0,
+              sweep_angle_axis=sweep, semi_major_axis=a, inverse_flattening=rf,
+              false_easting=false_easting, false_northing=false_northing)
+    return CRS("CF", "geos", f"Geostationary view over {lon_0:g} deg ({ell})", "geos", "en", cf,
+               (ell, lon_0, 0.0, 1.0, false_easting, false_northing, height, sweep, a, rf))
+
+
+def _geostationary_from_cf(attrs: dict) -> CRS:
+    if float(attrs.get("latitude_of_projection_origin", 0.0)) != 0.0:
+        raise ValueError("geostationary needs latitude_of_projection_origin 0, was "
+                         f"{attrs['latitude_of_projection_origin']}")
+    sweep = attrs.get("sweep_angle_axis")
+    if sweep is None and "fixed_angle_axis" in attrs:   # the complement
+        sweep = {"x": "y", "y": "x"}.get(str(attrs["fixed_angle_axis"]).lower(), "?")
+    sweep = "y" if sweep is None else str(sweep).lower()
+    a = float(attrs.get("semi_major_axis", _WGS84_A))
+    if "inverse_flattening" in attrs:
+        rf = float(attrs["inverse_flattening"])
+    elif "semi_minor_axis" in attrs:
+        rf = a / (a - float(attrs["semi_minor_axis"]))
+    else:
+        a, rf = _WGS84_A, _WGS84_RF
+    return geostationary_crs(float(attrs.get("longitude_of_projection_origin", 0.0)),
+                             float(attrs["perspective_point_height"]), sweep, a, rf,
+                             float(attrs.get("false_easting", 0.0)),
+                             float(attrs.get("false_northing", 0.0)))
+
 
 def rotated_pole_crs(pole_lat: float, pole_lon: float, pole_grid_lon: float = 0.0) -> CRS:
     """A CF rotated latitude-longitude grid (``rotated_latitude_longitude``,
@@ -438,6 +526,19 @@ def _ellipsoid(name: str):
     return GRS80 if name == "GRS 1980" else WGS84
 
 
+def _conic_or_geos(crs: CRS):
+    """(ellipsoid, projections.py object) of an lcc or geos CRS."""
+    from .projections import Ellipsoid, Geostationary, LambertConformalConic
+    if crs.kind == "geos":
+        height, sweep, a, rf = crs.params[6:10]
+        ell = Ellipsoid(crs.params[0], a, rf)
+        return ell, Geostationary(ell, height, sweep)
+    ell = _ellipsoid(crs.params[0])
+    lat_0, k0, lat_1, lat_2 = crs.params[2], crs.params[3], crs.params[6], crs.params[7]
+    return ell, LambertConformalConic(ell, lat_0 * _DEG_TO_RAD, lat_1 * _DEG_TO_RAD,
+                                      lat_2 * _DEG_TO_RAD, k0)
+
+
 def _adjlon(lam):
     """PROJ adjlon: wrap to [-pi, pi] when outside by more than the tolerance."""
     lam = np.asarray(lam, dtype=np.float64)
@@ -473,7 +574,9 @@ def _projection(crs: CRS):
         ell = _ellipsoid(ell_name)
         lam0 = lon_0 * _DEG_TO_RAD
         phi0 = lat_0 * _DEG_TO_RAD
-        if crs.kind == "stere":
+        if crs.kind in ("lcc", "geos"):
+            ell, proj = _conic_or_geos(crs)
+        elif crs.kind == "stere":
             lat_ts = crs.params[6]
             proj = PolarStereographic(ell, phi0, None if lat_ts is None
                                       else lat_ts * _DEG_TO_RAD, k0)
@@ -488,11 +591,16 @@ def _projection(crs: CRS):
             x, y = proj.forward(lam, phi)
             return a * x + x_0, a * y + y_0
 
-        def inverse(x, y, proj=proj, lam0=lam0, ra=ra, x_0=x_0, y_0=y_0):
+        def inverse(x, y, proj=proj, lam0=lam0, ra=ra, x_0=x_0, y_0=y_0,
+                    keep_inf=crs.kind == "geos"):
             xx = (np.asarray(x, dtype=np.float64) - x_0) * ra
             yy = (np.asarray(y, dtype=np.float64) - y_0) * ra
             lam, phi = proj.inverse(xx, yy)
-            lam = _adjlon(lam + lam0)
+            if keep_inf:   # off the geos disc both results stay +inf
+                with np.errstate(invalid="ignore"):
+                    lam = np.where(lam == np.inf, lam, _adjlon(lam + lam0))
+            else:
+                lam = _adjlon(lam + lam0)
             return lam * _RAD_TO_DEG_FACTOR, phi * _RAD_TO_DEG_FACTOR
 
         hit = (forward, inverse)
@@ -523,8 +631,21 @@ def _proj_step(crs: CRS, inverse: bool):
     ell = _ellipsoid(ell_name)
     st.a, st.ra, st.x0, st.y0 = ell.a, 1.0 / ell.a, x_0, y_0
     st.lam0, st.phi0 = lon_0 * _DEG_TO_RAD, lat_0 * _DEG_TO_RAD
+    if crs.kind in ("lcc", "geos"):
+        ell, proj = _conic_or_geos(crs)
+        st.a, st.ra = ell.a, 1.0 / ell.a
     st.e, st.es, st.one_es = ell.e, ell.es, ell.one_es
-    if crs.kind == "tmerc":
+    if crs.kind == "lcc":
+        st.kind = PROJ_KINDS["lcc_inv" if inverse else "lcc_fwd"]
+        for k, v in enumerate([proj.n, proj.c, proj.rho0, proj.k0] + list(proj.cgb)):
+            st.c[k] = v
+    elif crs.kind == "geos":
+        st.kind = PROJ_KINDS["geos_inv" if inverse else "geos_fwd"]
+        st.mode = 1 if proj.flip else 0
+        for k, v in enumerate([proj.radius_g, proj.radius_g_1, proj.C, proj.radius_p,
+                               proj.radius_p_inv2]):
+            st.c[k] = v
+    elif crs.kind == "tmerc":
         proj = TransverseMercator(ell, k0, st.phi0)
         st.kind = PROJ_KINDS["tmerc_inv" if inverse else "tmerc_fwd"]
         for k, v in enumerate(list(proj.cgb) + list(proj.cbg) + list(proj.utg) + list(proj.gtu)):

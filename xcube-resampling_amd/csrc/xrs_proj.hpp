@@ -5,8 +5,9 @@
 // operation order, -ffp-contract=off): web Mercator (merc_s, webmerc),
 // transverse Mercator (tmerc poder_engsager: Clenshaw gatg / clenS),
 // Lambert azimuthal equal area (laea e_forward / e_inverse) and polar
-// stereographic (stere e_forward / e_inverse, N_POLE / S_POLE), around PROJ's
-// pj_fwd / pj_inv (lam0 + adjlon, unit-ellipsoid scaling, false origin), and
+// stereographic (stere e_forward / e_inverse, N_POLE / S_POLE), Lambert conformal
+// conic (lcc, 1SP / 2SP) and the geostationary view (geos, both sweep axes), around
+// PROJ's pj_fwd / pj_inv (lam0 + adjlon, unit-ellipsoid scaling, false origin), and
 // the rotated pole (ob_tran o_forward / o_inverse around longlat).
 // The device libm differs from the host's in the last bit of some
 // transcendentals, so results agree with the numpy restatement to a few ulps.
@@ -332,6 +333,118 @@ __device__ inline void stere_inv(const XrsProjStep& s, double x, double y, doubl
   phi = south ? -ph : ph;
 }
 
+// ---- Lambert conformal conic (projections.py LambertConformalConic) -----------------
+// PROJ lcc.cpp on the ellipsoid, 1SP and 2SP.  s.c[0]: n; s.c[1]: c; s.c[2]: rho0;
+// s.c[3]: k0; s.c[4..9]: cgb.  The cone's apex lies over the north pole for
+// n > 0 and over the south pole for n < 0 (c < 0 then, so rho = c ts^n too).
+__device__ inline void lcc_fwd(const XrsProjStep& s, double lam, double phi, double& x,
+                               double& y) {
+  const double n = s.c[0];
+  double sinphi, cosphi, sinl, cosl;
+  sincos(phi, &sinphi, &cosphi);
+  // pow as exp(n log ts): ts > 0 for |phi| < pi/2, NaN beyond as in PROJ
+  double rho = s.c[1] * exp(n * log(tsfn(sinphi, cosphi, s.e)));
+  const bool pole = fabs(fabs(phi) - kHalfPi) < kEps10;
+  const bool bad = pole && phi * n <= 0.0;   // the pole opposite the apex
+  rho = pole ? 0.0 : rho;
+  sincos(n * lam, &sinl, &cosl);
+  const double xx = s.c[3] * (rho * sinl);
+  const double yy = s.c[3] * (s.c[2] - rho * cosl);
+  x = bad ? INFINITY : xx;
+  y = bad ? INFINITY : yy;
+}
+
+// ts = (rho / c)^(1/n) is tsfn of the latitude, so the latitude follows as in
+// stere_inv: chi = pi/2 - 2 atan(ts) through the conformal -> geodetic series,
+// not PROJ's pj_phi2 iteration (a data-dependent exit diverges on a wave)
+__device__ inline void lcc_inv(const XrsProjStep& s, double x, double y, double& lam,
+                               double& phi) {
+  const double n = s.c[0];
+  const bool south = n < 0.0;
+  x = x / s.c[3];
+  y = s.c[2] - y / s.c[3];
+  // |x|, |y| are a few earth radii at most: no scaling needed
+  double rho = sqrt(x * x + y * y);
+  const bool apex = rho == 0.0;
+  if (south) {
+    rho = -rho;
+    x = -x;
+    y = -y;
+  }
+  const double t = exp(log(rho / s.c[1]) * (1.0 / n));
+  const double t2 = t * t;
+  const double den = 1.0 + t2;
+  const double sin_chi = (1.0 - t2) / den;
+  const double cos_chi = (t + t) / den;
+  const double chi = kHalfPi - 2.0 * atan(t);
+  const double sin_2chi = 2.0 * sin_chi * cos_chi;
+  const double cos_2chi = (cos_chi - sin_chi) * (cos_chi + sin_chi);
+  const double ph = gatg(s.c + 4, chi, cos_2chi, sin_2chi);
+  lam = apex ? 0.0 : atan2_pp(x, y) / n;
+  phi = apex ? (south ? -kHalfPi : kHalfPi) : ph;
+}
+
+// ---- geostationary satellite view (projections.py Geostationary) ---------------------
+// PROJ geos.cpp on the ellipsoid.  s.c[0]: radius_g = 1 + h / a; s.c[1]: radius_g_1 =
+// h / a; s.c[2]: C = radius_g^2 - 1; s.c[3]: radius_p = sqrt(1 - es); s.c[4]:
+// 1 / (1 - es); s.mode: 0 sweep y, 1 sweep x (PROJ's flip_axis).  Both steps end
+// in selects over values every lane has computed: no lane leaves without a result.
+//
+// Forward: PROJ's geocentric latitude atan((1 - es) tan phi) and radius
+// radius_p / hypot(radius_p cos, sin) give the vector w (cos phi cos lam, cos phi
+// sin lam, (1 - es) sin phi) with w = 1 / sqrt(cos^2 phi + (1 - es) sin^2 phi): no
+// tan / atan pair.  The point is seen where (radius_g - Vx) Vx - Vy^2 - Vz^2 / (1 - es)
+// >= 0; elsewhere both outputs are +inf.  radius_g - Vx > 0 always, so the two
+// arctangents of quotients are atan2_pp.
+__device__ inline void geos_fwd(const XrsProjStep& s, double lam, double phi, double& x,
+                                double& y) {
+  double sinlam, coslam, sinphi, cosphi;
+  sincos(lam, &sinlam, &coslam);
+  sincos(phi, &sinphi, &cosphi);
+  const double pz = s.one_es * sinphi;
+  const double w = 1.0 / sqrt(cosphi * cosphi + pz * sinphi);
+  const double r = w * cosphi;
+  const double Vx = r * coslam, Vy = r * sinlam, Vz = w * pz;
+  const double tmp = s.c[0] - Vx;
+  const bool bad = (tmp * Vx - Vy * Vy - Vz * Vz * s.c[4]) < 0.0;
+  const bool flip = s.mode == 1;
+  const double other = flip ? Vz : Vy;
+  const double h = sqrt(other * other + tmp * tmp);
+  const double ax = atan2_pp(Vy, flip ? h : tmp);
+  const double ay = atan2_pp(Vz, flip ? tmp : h);
+  x = bad ? INFINITY : s.c[1] * ax;
+  y = bad ? INFINITY : s.c[1] * ay;
+}
+
+// Inverse: the ray (-1, Vy, Vz) from the satellite meets the ellipsoid where the
+// quadratic a k^2 - 2 radius_g k + C = 0, a = 1 + q, has its smaller root; its
+// discriminant over 4 is radius_g^2 - a C = 1 - q C (terms of size 1 where PROJ's
+// b^2 - 4 a C cancels terms of size 175 towards the limb); where it is negative the
+// ray passes the limb: both outputs +inf.  The hit point has Vx = radius_g - k > 0,
+// so PROJ's atan(Vz cos(lam) / Vx) is atan(Vz / hypot(Vx, Vy)) and the geodetic
+// latitude one atan2_pp of (Vz / (1 - es), hypot(Vx, Vy)).
+__device__ inline void geos_inv(const XrsProjStep& s, double x, double y, double& lam,
+                                double& phi) {
+  const bool flip = s.mode == 1;
+  const double tx = tan(x / s.c[1]), ty = tan(y / s.c[1]);
+  const double first = flip ? ty : tx;
+  const double stretch = sqrt(1.0 + first * first);
+  double Vy = flip ? tx * stretch : tx;
+  double Vz = flip ? ty : ty * stretch;
+  const double zp = Vz / s.c[3];
+  const double q = Vy * Vy + zp * zp;
+  const double det = 1.0 - q * s.c[2];
+  const bool bad = det < 0.0;
+  const double k = (s.c[0] - sqrt(bad ? 0.0 : det)) / (1.0 + q);
+  const double Vx = s.c[0] - k;
+  Vy = Vy * k;
+  Vz = Vz * k;
+  const double l = atan2_pp(Vy, Vx);
+  const double p = atan2_pp(s.c[4] * Vz, sqrt(Vx * Vx + Vy * Vy));
+  lam = bad ? INFINITY : l;
+  phi = bad ? INFINITY : p;
+}
+
 // ---- rotated pole (projections.py RotatedPole) ---------------------------------------
 // s.c[0], s.c[1]: sin / cos of the pole's latitude; s.c[2]: north_pole_grid_longitude;
 // s.lam0: the pole's longitude + 180 deg.  PROJ aatan2 (0 where both vanish: the
@@ -489,23 +602,32 @@ __device__ inline void apply_step(const XrsProjStep& s, double& x, double& y) {
     x = lam * rad_to_deg;
     y = phi * rad_to_deg;
   } else if constexpr (KIND == XRS_PROJ_TMERC_FWD || KIND == XRS_PROJ_LAEA_FWD ||
-                       KIND == XRS_PROJ_STERE_FWD) {
+                       KIND == XRS_PROJ_STERE_FWD || KIND == XRS_PROJ_LCC_FWD ||
+                       KIND == XRS_PROJ_GEOS_FWD) {
     const double lam = adjlon(x * kDegToRad - s.lam0);
     const double phi = y * kDegToRad;
     double px, py;
     if constexpr (KIND == XRS_PROJ_TMERC_FWD) tmerc_fwd(s, lam, phi, px, py);
     else if constexpr (KIND == XRS_PROJ_LAEA_FWD) laea_fwd(s, lam, phi, px, py);
+    else if constexpr (KIND == XRS_PROJ_LCC_FWD) lcc_fwd(s, lam, phi, px, py);
+    else if constexpr (KIND == XRS_PROJ_GEOS_FWD) geos_fwd(s, lam, phi, px, py);
     else stere_fwd(s, lam, phi, px, py);
     x = s.a * px + s.x0;
     y = s.a * py + s.y0;
   } else if constexpr (KIND == XRS_PROJ_TMERC_INV || KIND == XRS_PROJ_LAEA_INV ||
-                       KIND == XRS_PROJ_STERE_INV) {
+                       KIND == XRS_PROJ_STERE_INV || KIND == XRS_PROJ_LCC_INV ||
+                       KIND == XRS_PROJ_GEOS_INV) {
     const double xx = (x - s.x0) * s.ra, yy = (y - s.y0) * s.ra;
     double lam, phi;
     if constexpr (KIND == XRS_PROJ_TMERC_INV) tmerc_inv(s, xx, yy, lam, phi);
     else if constexpr (KIND == XRS_PROJ_LAEA_INV) laea_inv(s, xx, yy, lam, phi);
+    else if constexpr (KIND == XRS_PROJ_LCC_INV) lcc_inv(s, xx, yy, lam, phi);
+    else if constexpr (KIND == XRS_PROJ_GEOS_INV) geos_inv(s, xx, yy, lam, phi);
     else stere_inv(s, xx, yy, lam, phi);
-    lam = adjlon(lam + s.lam0);
+    // off the geos disc both outputs stay +inf (adjlon would turn the longitude
+    // into NaN, as it does for tmerc and laea, whose results are kept as they are)
+    if constexpr (KIND == XRS_PROJ_GEOS_INV) lam = lam == INFINITY ? lam : adjlon(lam + s.lam0);
+    else lam = adjlon(lam + s.lam0);
     x = lam * rad_to_deg;
     y = phi * rad_to_deg;
   } else if constexpr (KIND == XRS_PROJ_ROTPOLE_FWD) {
@@ -518,7 +640,7 @@ __device__ inline void apply_step(const XrsProjStep& s, double& x, double& y) {
 // ---- the pipelines the launch tables take (host) ----------------------------------
 // XRS_PROJ_* kinds come in pairs: odd forward (to the CRS), even inverse
 inline bool is_valid(int kind) {
-  return kind >= XRS_PROJ_WEBMERC_FWD && kind <= XRS_PROJ_ROTPOLE_INV;
+  return kind >= XRS_PROJ_WEBMERC_FWD && kind <= XRS_PROJ_GEOS_INV;
 }
 inline bool is_forward(int kind) { return is_valid(kind) && (kind & 1) != 0; }
 
@@ -542,6 +664,8 @@ int dispatch_second(int k1, Fn&& fn) {
     XRS_K1(XRS_PROJ_LAEA_FWD)
     XRS_K1(XRS_PROJ_STERE_FWD)
     XRS_K1(XRS_PROJ_ROTPOLE_FWD)
+    XRS_K1(XRS_PROJ_LCC_FWD)
+    XRS_K1(XRS_PROJ_GEOS_FWD)
 #undef XRS_K1
     default: return XRS_ERR_ARG;
   }
@@ -560,11 +684,15 @@ int dispatch_pipeline(int k0, int k1, Fn&& fn) {
     XRS_K0F(XRS_PROJ_LAEA_FWD)
     XRS_K0F(XRS_PROJ_STERE_FWD)
     XRS_K0F(XRS_PROJ_ROTPOLE_FWD)
+    XRS_K0F(XRS_PROJ_LCC_FWD)
+    XRS_K0F(XRS_PROJ_GEOS_FWD)
     XRS_K0I(XRS_PROJ_WEBMERC_INV)
     XRS_K0I(XRS_PROJ_TMERC_INV)
     XRS_K0I(XRS_PROJ_LAEA_INV)
     XRS_K0I(XRS_PROJ_STERE_INV)
     XRS_K0I(XRS_PROJ_ROTPOLE_INV)
+    XRS_K0I(XRS_PROJ_LCC_INV)
+    XRS_K0I(XRS_PROJ_GEOS_INV)
 #undef XRS_K0F
 #undef XRS_K0I
     default: return XRS_ERR_ARG;

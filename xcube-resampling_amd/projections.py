@@ -16,6 +16,10 @@ PROJ's ``pj_fwd`` / ``pj_inv`` do):
   ``pj_authlat``);
 * ``PolarStereographic`` — PROJ ``stere`` in its two polar aspects on the
   ellipsoid (EPSG methods 9810 variant A: ``k0``, 9829 variant B: ``lat_ts``);
+* ``LambertConformalConic`` — PROJ ``lcc`` on the ellipsoid, one or two standard
+  parallels (EPSG methods 9801 / 9802; EPSG:3034, EPSG:2154);
+* ``Geostationary`` — PROJ ``geos`` on the ellipsoid, both sweep axes (CF
+  ``geostationary``);
 * ``RotatedPole`` — PROJ ``ob_tran +o_proj=longlat`` as CF's
   ``rotated_latitude_longitude`` defines it (degrees on both sides).
 
@@ -387,6 +391,139 @@ class PolarStereographic:
         phi = _gatg(self.cgb, chi, cos_2chi, sin_2chi)
         lam = np.where((x == 0.0) & (y == 0.0), 0.0, np.arctan2(x, y))
         return lam, (-phi if self.south else phi)
+
+
+# ---- Lambert conformal conic (PROJ lcc.cpp on the ellipsoid, 1SP and 2SP) ----------
+def _msfn(sinphi, cosphi, es):
+    return cosphi / math.sqrt(1.0 - es * sinphi * sinphi)
+
+
+class LambertConformalConic:
+    """PROJ lcc, ellipsoidal (lcc_e_forward / lcc_e_inverse).  ``phi1 == phi2``
+    is the 1SP form; n < 0 puts the cone's apex over the south pole (c < 0
+    then).  The power is exp(n log ts); the inverse takes the latitude from
+    ts = (rho / c)^(1/n) by the series PolarStereographic.inverse uses, in
+    place of PROJ's ``pj_phi2`` iteration."""
+
+    def __init__(self, ell: Ellipsoid, phi0: float, phi1: float, phi2: float, k0: float = 1.0):
+        if abs(phi1 + phi2) < _EPS10:
+            raise ValueError("LambertConformalConic: lat_1 = -lat_2 is no cone")
+        self.ell = ell
+        self.k0 = k0
+        e, es = ell.e, ell.es
+        sinphi, cosphi = math.sin(phi1), math.cos(phi1)
+        n = sinphi
+        m1 = _msfn(sinphi, cosphi, es)
+        ml1 = float(_tsfn(sinphi, cosphi, e))
+        if abs(phi1 - phi2) >= _EPS10:   # secant cone
+            sinphi, cosphi = math.sin(phi2), math.cos(phi2)
+            n = math.log(m1 / _msfn(sinphi, cosphi, es))
+            n /= math.log(ml1 / float(_tsfn(sinphi, cosphi, e)))
+        self.n = n
+        self.c = m1 * math.pow(ml1, -n) / n
+        self.rho0 = 0.0 if abs(abs(phi0) - _HALFPI) < _EPS10 else \
+            self.c * math.pow(float(_tsfn(math.sin(phi0), math.cos(phi0), e)), n)
+        self.cgb = TransverseMercator(ell, 1.0).cgb
+
+    def forward(self, lam, phi):
+        lam = np.asarray(lam, dtype=np.float64)
+        phi = np.asarray(phi, dtype=np.float64)
+        n = self.n
+        sinphi, cosphi = np.sin(phi), np.cos(phi)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rho = self.c * np.exp(n * np.log(_tsfn(sinphi, cosphi, self.ell.e)))
+        pole = np.abs(np.abs(phi) - _HALFPI) < _EPS10
+        bad = pole & (phi * n <= 0.0)   # the pole opposite the apex
+        rho = np.where(pole, 0.0, rho)
+        sinl, cosl = np.sin(n * lam), np.cos(n * lam)
+        x = self.k0 * (rho * sinl)
+        y = self.k0 * (self.rho0 - rho * cosl)
+        return np.where(bad, np.inf, x), np.where(bad, np.inf, y)
+
+    def inverse(self, x, y):
+        n = self.n
+        x = np.asarray(x, dtype=np.float64) / self.k0
+        y = self.rho0 - np.asarray(y, dtype=np.float64) / self.k0
+        rho = np.sqrt(x * x + y * y)   # a few earth radii at most: no scaling
+        apex = rho == 0.0
+        if n < 0.0:
+            rho, x, y = -rho, -x, -y
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t = np.exp(np.log(rho / self.c) * (1.0 / n))
+            t2 = t * t
+            den = 1.0 + t2
+            sin_chi = (1.0 - t2) / den
+            cos_chi = (t + t) / den
+            chi = _HALFPI - 2.0 * np.arctan(t)
+            sin_2chi = 2.0 * sin_chi * cos_chi
+            cos_2chi = (cos_chi - sin_chi) * (cos_chi + sin_chi)
+            phi = _gatg(self.cgb, chi, cos_2chi, sin_2chi)
+            lam = np.where(apex, 0.0, np.arctan2(x, y) / n)
+        return lam, np.where(apex, -_HALFPI if n < 0.0 else _HALFPI, phi)
+
+
+# ---- Geostationary satellite view (PROJ geos.cpp on the ellipsoid) -----------------
+class Geostationary:
+    """PROJ geos, ellipsoidal (e_forward / e_inverse), ``h`` the perspective point
+    height in metres, ``sweep`` "y" (PROJ's default: Meteosat, Himawari) or "x"
+    (GOES).  Coordinates are scan angles times h / a on the unit ellipsoid.  The
+    operations are the device's (xrs_proj.hpp geos_fwd / geos_inv): PROJ's
+    geocentric latitude and radius folded into w = 1 / sqrt(cos^2 + (1 - es)
+    sin^2), the arctangents of quotients as arctan2 (their second arguments are
+    positive).  Where the satellite does not see the point (forward) or the ray
+    passes the limb (inverse) both results are +inf."""
+
+    def __init__(self, ell: Ellipsoid, h: float, sweep: str = "y"):
+        if sweep not in ("x", "y"):
+            raise ValueError(f"geos sweep axis must be 'x' or 'y', was {sweep!r}")
+        self.ell = ell
+        self.flip = sweep == "x"
+        self.radius_g_1 = h / ell.a
+        self.radius_g = 1.0 + self.radius_g_1
+        self.C = self.radius_g * self.radius_g - 1.0
+        self.radius_p = math.sqrt(ell.one_es)
+        self.radius_p_inv2 = 1.0 / ell.one_es
+
+    def forward(self, lam, phi):
+        lam = np.asarray(lam, dtype=np.float64)
+        phi = np.asarray(phi, dtype=np.float64)
+        sinlam, coslam = np.sin(lam), np.cos(lam)
+        sinphi, cosphi = np.sin(phi), np.cos(phi)
+        pz = self.ell.one_es * sinphi
+        w = 1.0 / np.sqrt(cosphi * cosphi + pz * sinphi)
+        r = w * cosphi
+        Vx, Vy, Vz = r * coslam, r * sinlam, w * pz
+        tmp = self.radius_g - Vx
+        with np.errstate(invalid="ignore"):
+            bad = (tmp * Vx - Vy * Vy - Vz * Vz * self.radius_p_inv2) < 0.0
+        other = Vz if self.flip else Vy
+        h = np.sqrt(other * other + tmp * tmp)
+        ax = np.arctan2(Vy, h if self.flip else tmp)
+        ay = np.arctan2(Vz, tmp if self.flip else h)
+        return (np.where(bad, np.inf, self.radius_g_1 * ax),
+                np.where(bad, np.inf, self.radius_g_1 * ay))
+
+    def inverse(self, x, y):
+        x = np.asarray(x, dtype=np.float64)
+        y = np.asarray(y, dtype=np.float64)
+        tx, ty = np.tan(x / self.radius_g_1), np.tan(y / self.radius_g_1)
+        first = ty if self.flip else tx
+        stretch = np.sqrt(1.0 + first * first)
+        Vy = tx * stretch if self.flip else tx
+        Vz = ty if self.flip else ty * stretch
+        zp = Vz / self.radius_p
+        q = Vy * Vy + zp * zp
+        # a quarter of PROJ's b^2 - 4 a C (a = 1 + q), without its cancellation
+        det = 1.0 - q * self.C
+        with np.errstate(invalid="ignore"):
+            bad = det < 0.0
+        k = (self.radius_g - np.sqrt(np.where(bad, 0.0, det))) / (1.0 + q)
+        Vx = self.radius_g - k
+        Vy = Vy * k
+        Vz = Vz * k
+        lam = np.arctan2(Vy, Vx)
+        phi = np.arctan2(self.radius_p_inv2 * Vz, np.sqrt(Vx * Vx + Vy * Vy))
+        return np.where(bad, np.inf, lam), np.where(bad, np.inf, phi)
 
 
 # ---- Rotated pole (PROJ ob_tran.cpp o_forward / o_inverse around longlat) ----------
