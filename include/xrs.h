@@ -599,6 +599,45 @@ int xrs_reproject_proj(const void* src, int src_dtype, int64_t n, int64_t src_h,
                        double x_res, double y_res, int interp, double fill,
                        int32_t* err_flags, void* stream);
 
+/* -------------------------------------------------------------------------
+ * xrs_coords_stats (K8) — the full-raster part of the 2-D branch of
+ * new_grid_mapping_from_coords (gridmapping/coords.py:99-327) in one pass over
+ * the coordinates x, y (h, w) float64, rows contiguous, row_stride elements
+ * between rows:
+ *  - any_gt_180: any(x > 180), the reference's is_lon_360 test;
+ *  - the extremes of _estimate_2d_resolution (coords.py:226-264): per pixel
+ *    (j, i), in numpy's operation order and without FMA contraction,
+ *      dxx = |x[j, i+1] - x[j, i]|, dxy = |x[j+1, i] - x[j, i]|, dyx, dyy from y
+ *      (the last column takes column w-2's x-direction difference, the last
+ *      row takes row h-2's y-direction difference; a NaN difference or one
+ *      <= 1e-8 counts as 0, an infinite one stays infinite),
+ *      ax = sqrt(dxx*dxx + dxy*dxy), ay = sqrt(dyx*dyx + dyy*dyy),
+ *      geographic != 0: xr = ax * (pi/180), yr = ay * (pi/180),
+ *                       ax = (6371000 * cos(xr)) * yr, ay = 6371000 * yr,
+ *      area = ax * ay.
+ *    Only areas > 0 take part (+inf does).  area_min / area_max with their
+ *    flat indices j * w + i (equal areas: the lowest index, as numpy's
+ *    nanargmin / nanargmax) and n_positive, the number of positive areas.
+ *    geographic == 0: the values are numpy's bit for bit; geographic != 0:
+ *    to the device cosine's error.  n_positive == 0: the areas are NaN, the
+ *    indices -1.
+ * out: one device record.  ws: xrs_coords_stats_workspace_size(h, w) bytes of
+ *   device memory, 8-byte aligned (one partial record per block; a second
+ *   small kernel folds them).  h < 2 or w < 2 (or either above 2^31 - 1,
+ *   row_stride < w): XRS_ERR_ARG.
+ * ------------------------------------------------------------------------- */
+typedef struct XrsCoordsStats {
+  double area_min, area_max;
+  int64_t idx_min, idx_max, n_positive;
+  int32_t any_gt_180;
+  int32_t pad;
+} XrsCoordsStats;
+
+int64_t xrs_coords_stats_workspace_size(int64_t h, int64_t w);
+int xrs_coords_stats(const double* x, const double* y, int64_t h, int64_t w,
+                     int64_t row_stride, int geographic, XrsCoordsStats* out, void* ws,
+                     int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

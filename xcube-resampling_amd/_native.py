@@ -164,7 +164,18 @@ _SIGNATURES = {
         _c_dbl, _c_dbl, _c_int, _c_dbl,                                          # res, interp, fill
         _c_ptr, _c_ptr,                                                          # flags, stream
     ]),
+    "xrs_coords_stats_workspace_size": (_c_i64, [_c_i64, _c_i64]),
+    "xrs_coords_stats": (_c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int,   # x .. geographic
+                                  _c_ptr, _c_ptr, _c_i64, _c_ptr]),          # out, ws, stream
 }
+
+
+class CoordsStats(ctypes.Structure):
+    """XrsCoordsStats (include/xrs.h): the result record of xrs_coords_stats."""
+
+    _fields_ = [("area_min", _c_dbl), ("area_max", _c_dbl), ("idx_min", _c_i64),
+                ("idx_max", _c_i64), ("n_positive", _c_i64), ("any_gt_180", ctypes.c_int32),
+                ("pad", ctypes.c_int32)]
 
 
 class ProjStep(ctypes.Structure):

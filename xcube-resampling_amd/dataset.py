@@ -178,7 +178,16 @@ class DataArray:
             i = key.index(Ellipsis)
             key = key[:i] + (slice(None),) * (self.ndim - len(key) + 1) + key[i + 1:]
         key = key + (slice(None),) * (self.ndim - len(key))
-        data = self._data[key]
+        data, data_key = self._data, key
+        if _is_torch(data):
+            # torch has no negative strides: a reversing slice selects its rows (a copy)
+            import torch
+            for axis, k in enumerate(key):
+                if isinstance(k, slice) and (k.step or 1) < 0:
+                    idx = torch.arange(*k.indices(data.shape[axis]), device=data.device)
+                    data = data.index_select(axis, idx)
+                    data_key = data_key[:axis] + (slice(None),) + data_key[axis + 1:]
+        data = data[data_key]
         dims = tuple(d for d, k in zip(self._dims, key) if not isinstance(k, (int, np.integer)))
         chunks = None
         if self._chunks is not None:

@@ -2,12 +2,14 @@
 
 from __future__ import annotations
 
+import collections
 import math
 
 import numpy as np
 
 from ..crs import normalize_crs
 from ..dataset import DataArray
+from ..options import get_options
 from .base import DEFAULT_TOLERANCE, GridMapping, _assert
 from .helpers import (
     _default_xy_var_names,
@@ -84,6 +86,70 @@ def _as_data_array(c, name) -> DataArray:
     raise TypeError(f"{name} must be an instance of DataArray")
 
 
+_Edges2D = collections.namedtuple(
+    "_Edges2D", "x_top x_bottom x_left x_right y_top y_bottom y_left y_right")
+
+
+def _edges_2d(x, y) -> _Edges2D:
+    """First / last row and column of the (h, w) coordinates as numpy vectors:
+    views of numpy arrays, one small read-back of device tensors."""
+    if isinstance(x, np.ndarray):
+        return _Edges2D(x[0], x[-1], x[:, 0], x[:, -1], y[0], y[-1], y[:, 0], y[:, -1])
+    import torch
+    h, w = x.shape
+    flat = torch.cat([x[0], x[-1], x[:, 0], x[:, -1], y[0], y[-1], y[:, 0], y[:, -1]])
+    return _Edges2D(*np.split(flat.cpu().numpy(), np.cumsum([w, w, h, h, w, w, h])))
+
+
+def _device_coords_2d(x_coords: DataArray, y_coords: DataArray):
+    """The 2-D coordinates as a pair of float64 device tensors when their
+    analysis runs on the device: device tensors always, numpy arrays of at
+    least ``coords_device_min_points`` points (uploaded here, once) when a
+    HIP device is present.  None: the numpy analysis, as the reference's."""
+    from ..device import is_device_array, torch
+    x, y = x_coords.data, y_coords.data
+    if min(x.shape) < 2:
+        return None
+    if is_device_array(x) and is_device_array(y):
+        if x.device == y.device and x.dtype == y.dtype == torch().float64:
+            return x, y
+        return None
+    if isinstance(x, np.ndarray) and isinstance(y, np.ndarray) \
+            and x.dtype == y.dtype == np.float64 \
+            and x.size >= get_options()["coords_device_min_points"] \
+            and torch().cuda.is_available():
+        from ..streaming import host_to_device
+        device = torch().device("cuda", torch().cuda.current_device())
+        return host_to_device(x, device), host_to_device(y, device)
+    return None
+
+
+def _device_area_extremes(stats, x, y, crs):
+    """(area_min, area_max) of _estimate_2d_resolution from K8's record.
+    Projected CRS: K8's values (numpy's bit for bit).  Geographic CRS: numpy's
+    cosine is not the device's, so the two areas are recomputed here with the
+    numpy expressions on the points around idx_min / idx_max: the values are
+    numpy's own, only the choice between pixels whose areas lie within the
+    device cosine's error of each other can differ."""
+    if stats.n_positive == 0:
+        raise ValueError("All-NaN slice encountered")   # np.nanargmin's
+    if not crs.is_geographic:
+        return stats.area_min, stats.area_max
+    import torch
+    h, w = x.shape
+    j = [stats.idx_min // w, stats.idx_max // w]
+    i = [stats.idx_min % w, stats.idx_max % w]
+    # the concatenations: the last column / row repeats the difference before it
+    jb = [k + 1 if k + 1 < h else h - 2 for k in j]
+    ib = [k + 1 if k + 1 < w else w - 2 for k in i]
+    rows, cols = j + j + jb, i + ib + i
+    p = torch.stack([x[rows, cols], y[rows, cols]]).cpu().numpy()
+    (x0, xi, xj), (y0, yi, yj) = np.split(p[0], 3), np.split(p[1], 3)
+    areas = _cell_areas(_abs_no_nan(xi - x0), _abs_no_nan(xj - x0),
+                        _abs_no_nan(yi - y0), _abs_no_nan(yj - y0), crs)
+    return float(areas[0]), float(areas[1])
+
+
 def new_grid_mapping_from_coords(x_coords, y_coords, crs, *, xy_res=None, xy_bbox=None,
                                  tile_size=None, tolerance: float = DEFAULT_TOLERANCE
                                  ) -> GridMapping:
@@ -103,13 +169,13 @@ def new_grid_mapping_from_coords(x_coords, y_coords, crs, *, xy_res=None, xy_bbo
 
     tile_size = _normalize_int_pair(tile_size, default=None)
     is_lon_360 = None
-    if crs.is_geographic:
-        is_lon_360 = bool(np.any(x_coords.values > 180))
 
     if x_coords.ndim == 1:
         cls = Coords1DGridMapping
         _assert(x_coords.size >= 2 and y_coords.size >= 2,
                 "sizes of x_coords and y_coords 1D arrays must be >= 2")
+        if crs.is_geographic:
+            is_lon_360 = bool(np.any(x_coords.values > 180))
         size = x_coords.size, y_coords.size
         x_dim, y_dim = x_coords.dims[0], y_coords.dims[0]
         x_diff = _abs_no_zero(np.diff(x_coords.values))
@@ -138,6 +204,8 @@ def new_grid_mapping_from_coords(x_coords, y_coords, crs, *, xy_res=None, xy_bbo
             tile_size = (max(0, *x_coords.chunks[0]), max(0, *y_coords.chunks[0]))
         yv = y_coords.values
         is_j_axis_up = bool(yv[0] < yv[-1])
+        xv = x_coords.values
+        x_first, x_last, y_first, y_last = xv[0], xv[-1], yv[0], yv[-1]
     else:
         cls = Coords2DGridMapping
         _assert(x_coords.shape == y_coords.shape,
@@ -147,22 +215,45 @@ def new_grid_mapping_from_coords(x_coords, y_coords, crs, *, xy_res=None, xy_bbo
         y_dim, x_dim = x_coords.dims
         height, width = x_coords.shape
         size = width, height
-        x = x_coords.values
-        y = y_coords.values
+        # The two passes over every coordinate (any(x > 180) and the area
+        # extremes of _estimate_2d_resolution) run on the device (K8) for
+        # device tensors and large numpy arrays; everything else reads the
+        # four edges only, which then are all the host gets.
+        dev = _device_coords_2d(x_coords, y_coords) if xy_res is None else None
+        stats = None
+        from .. import kernels
+        if dev is not None:
+            if crs.is_geographic:
+                stats = kernels.coords_stats(dev[0], dev[1], True)
+                is_lon_360 = stats.any_gt_180
+            edges = _edges_2d(*dev)
+        else:
+            x = x_coords.values
+            y = y_coords.values
+            if crs.is_geographic:
+                is_lon_360 = bool(np.any(x > 180))
+            edges = _edges_2d(x, y)
         # the reference restricts these probes to the first dask chunk
         # (coords.py:197-200); numpy-backed coordinates form a single chunk
-        cs = x_coords.chunksize or x.shape
-        x_x_diff = _abs_no_nan(np.diff(x[0, :cs[1]]))
-        x_y_diff = _abs_no_nan(np.diff(x[:cs[0], 0]))
-        y_x_diff = _abs_no_nan(np.diff(y[0, :cs[0]]))
-        y_y_diff = _abs_no_nan(np.diff(y[:cs[1], 0]))
+        cs = x_coords.chunksize or (height, width)
+        x_x_diff = _abs_no_nan(np.diff(edges.x_top[:cs[1]]))
+        x_y_diff = _abs_no_nan(np.diff(edges.x_left[:cs[0]]))
+        y_x_diff = _abs_no_nan(np.diff(edges.y_top[:cs[0]]))
+        y_y_diff = _abs_no_nan(np.diff(edges.y_left[:cs[1]]))
         if not is_lon_360 and crs.is_geographic:
             if np.max(x_x_diff) > 180 or np.max(x_y_diff) > 180:
+                if dev is not None:   # the rare rewrite stays on the host
+                    x = x_coords.values
+                    y = y_coords.values
+                    y_coords = DataArray(y, y_coords.dims, y_coords.attrs, y_coords.name,
+                                         chunks=y_coords.chunks)
+                    dev = stats = None
                 x = to_lon_360(x)
                 x_coords = DataArray(x, x_coords.dims, x_coords.attrs, x_coords.name,
                                      chunks=x_coords.chunks)
-                x_x_diff = _abs_no_nan(np.diff(x[0, :]))
-                x_y_diff = _abs_no_nan(np.diff(x[:, 0]))
+                edges = _edges_2d(x, y)
+                x_x_diff = _abs_no_nan(np.diff(edges.x_top))
+                x_y_diff = _abs_no_nan(np.diff(edges.x_left))
                 is_lon_360 = True
         if xy_res is not None:
             x_res, y_res = _normalize_number_pair(xy_res)
@@ -174,7 +265,18 @@ def new_grid_mapping_from_coords(x_coords, y_coords, crs, *, xy_res=None, xy_bbo
                           and np.allclose(x_y_diff, 0, atol=tolerance)
                           and np.allclose(y_x_diff, 0, atol=tolerance))
         if not is_regular and xy_res is None:
-            x_res, y_res = _estimate_2d_resolution(x, y, crs)
+            if dev is not None:
+                if stats is None:
+                    stats = kernels.coords_stats(dev[0], dev[1], crs.is_geographic)
+                x_res, y_res = _resolution_from_areas(*_device_area_extremes(stats, *dev, crs),
+                                                      crs)
+            else:
+                x_res, y_res = _estimate_2d_resolution(x, y, crs)
+        if dev is not None:   # (an upload is handed on: rectification reuses it)
+            x_coords = DataArray(dev[0], x_coords.dims, x_coords.attrs, x_coords.name,
+                                 chunks=x_coords.chunks)
+            y_coords = DataArray(dev[1], y_coords.dims, y_coords.attrs, y_coords.name,
+                                 chunks=y_coords.chunks)
         if tile_size is None and x_coords.chunks is not None:
             j_chunks, i_chunks = x_coords.chunks
             tile_size = max(0, *i_chunks), max(0, *j_chunks)
@@ -182,24 +284,23 @@ def new_grid_mapping_from_coords(x_coords, y_coords, crs, *, xy_res=None, xy_bbo
             tile_width, tile_height = tile_size
             x_coords = x_coords.chunk({x_coords.dims[0]: tile_height, x_coords.dims[1]: tile_width})
             y_coords = y_coords.chunk({y_coords.dims[0]: tile_height, y_coords.dims[1]: tile_width})
-        ycs = (y_coords.chunksize or y.shape)[1]
-        is_j_axis_up = bool(np.all(y[0, :ycs] < y[-1, :ycs]))
+        ycs = (y_coords.chunksize or (height, width))[1]
+        is_j_axis_up = bool(np.all(edges.y_top[:ycs] < edges.y_bottom[:ycs]))
+        x_first, x_last, y_first, y_last = edges.x_left, edges.x_right, edges.y_top, edges.y_bottom
 
     _assert(x_res > 0 and y_res > 0, "internal error: x_res and y_res could not be determined",
             exception_type=RuntimeError)
     x_res, y_res = _to_int_or_float(x_res), _to_int_or_float(y_res)
     if xy_bbox is None:
-        xv = x_coords.values
-        yv = y_coords.values
         x_res_05, y_res_05 = x_res / 2, y_res / 2
-        x_min = _to_int_or_float(np.min(xv[..., 0]) - x_res_05)
-        x_max = _to_int_or_float(np.max(xv[..., -1]) + x_res_05)
+        x_min = _to_int_or_float(np.min(x_first) - x_res_05)
+        x_max = _to_int_or_float(np.max(x_last) + x_res_05)
         if is_j_axis_up:
-            y_min = _to_int_or_float(float(np.min(yv[0, ...])) - y_res_05)
-            y_max = _to_int_or_float(float(np.max(yv[-1, ...])) + y_res_05)
+            y_min = _to_int_or_float(float(np.min(y_first)) - y_res_05)
+            y_max = _to_int_or_float(float(np.max(y_last)) + y_res_05)
         else:
-            y_min = _to_int_or_float(float(np.min(yv[-1, ...])) - y_res_05)
-            y_max = _to_int_or_float(float(np.max(yv[0, ...])) + y_res_05)
+            y_min = _to_int_or_float(float(np.min(y_last)) - y_res_05)
+            y_max = _to_int_or_float(float(np.max(y_first)) + y_res_05)
         xy_bbox = (x_min, y_min, x_max, y_max)
 
     if cls is Coords1DGridMapping and is_regular:
@@ -214,6 +315,13 @@ def new_grid_mapping_from_coords(x_coords, y_coords, crs, *, xy_res=None, xy_bbo
 
 def _estimate_2d_resolution(x: np.ndarray, y: np.ndarray, crs):
     """coords.py:226-264 — area-based resolution estimate of irregular 2-D coords."""
+    xy_areas = _positive_areas(x, y, crs)
+    return _resolution_from_areas(xy_areas[np.nanargmin(xy_areas)],
+                                  xy_areas[np.nanargmax(xy_areas)], crs)
+
+
+def _positive_areas(x: np.ndarray, y: np.ndarray, crs) -> np.ndarray:
+    """coords.py:226-257 — the flattened per-pixel cell areas, NaN where not positive."""
     x_x_diff = _abs_no_nan(np.diff(x, axis=1))
     x_y_diff = _abs_no_nan(np.diff(x, axis=0))
     y_x_diff = _abs_no_nan(np.diff(y, axis=1))
@@ -222,17 +330,26 @@ def _estimate_2d_resolution(x: np.ndarray, y: np.ndarray, crs):
     y_x_diff_c = np.concatenate([y_x_diff, y_x_diff[:, -1:]], axis=1)
     x_y_diff_c = np.concatenate([x_y_diff, x_y_diff[-1:, :]], axis=0)
     y_y_diff_c = np.concatenate([y_y_diff, y_y_diff[-1:, :]], axis=0)
-    x_abs_diff = np.sqrt(np.square(x_x_diff_c) + np.square(x_y_diff_c))
-    y_abs_diff = np.sqrt(np.square(y_x_diff_c) + np.square(y_y_diff_c))
+    xy_areas = _cell_areas(x_x_diff_c, x_y_diff_c, y_x_diff_c, y_y_diff_c, crs).flatten()
+    return np.where(xy_areas > 0, xy_areas, np.nan)
+
+
+def _cell_areas(x_x_diff, x_y_diff, y_x_diff, y_y_diff, crs):
+    """coords.py:244-255 — per-pixel cell areas from the four absolute differences."""
+    x_abs_diff = np.sqrt(np.square(x_x_diff) + np.square(x_y_diff))
+    y_abs_diff = np.sqrt(np.square(y_x_diff) + np.square(y_y_diff))
     if crs.is_geographic:
         x_abs_diff_r = np.radians(x_abs_diff)
         y_abs_diff_r = np.radians(y_abs_diff)
         x_abs_diff = _ER * np.cos(x_abs_diff_r) * y_abs_diff_r
         y_abs_diff = _ER * y_abs_diff_r
-    xy_areas = (x_abs_diff * y_abs_diff).flatten()
-    xy_areas = np.where(xy_areas > 0, xy_areas, np.nan)
-    xy_res_min = math.sqrt(xy_areas[np.nanargmin(xy_areas)])
-    xy_res_max = math.sqrt(xy_areas[np.nanargmax(xy_areas)])
+    return x_abs_diff * y_abs_diff
+
+
+def _resolution_from_areas(area_min, area_max, crs):
+    """coords.py:258-264 — the resolution estimate from the extreme positive areas."""
+    xy_res_min = math.sqrt(area_min)
+    xy_res_max = math.sqrt(area_max)
     xy_res = 0.7 * xy_res_min + 0.3 * xy_res_max
     if crs.is_geographic:
         xy_res = math.degrees(xy_res / _ER)

@@ -344,6 +344,55 @@ def transform(transformer, x, y, grid: bool, device=None, stream=None):
     return ox, oy
 
 
+class CoordsStats:
+    """coords_stats' result: the positive cell-area extremes of the 2-D
+    coordinates with their flat indices (j * w + i), the number of positive
+    areas and any(x > 180).  ``n_positive == 0``: areas NaN, indices -1."""
+
+    __slots__ = ("area_min", "area_max", "idx_min", "idx_max", "n_positive", "any_gt_180")
+
+    def __init__(self, rec: _native.CoordsStats):
+        self.area_min, self.area_max = float(rec.area_min), float(rec.area_max)
+        self.idx_min, self.idx_max = int(rec.idx_min), int(rec.idx_max)
+        self.n_positive = int(rec.n_positive)
+        self.any_gt_180 = bool(rec.any_gt_180)
+
+    def __repr__(self) -> str:
+        return "CoordsStats(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__) + ")"
+
+
+def coords_stats(x, y, geographic: bool, stream=None) -> CoordsStats:
+    """K8 — the full-raster part of the 2-D branch of
+    new_grid_mapping_from_coords (gridmapping/coords.py:99-327) in one pass:
+    any(x > 180) and the positive-area extremes of _estimate_2d_resolution
+    (coords.py:226-264), see xrs_coords_stats.
+
+    x, y: (h, w) float64 device tensors (rows contiguous, any row stride; other
+    layouts are made contiguous first).  One read-back of the 48-byte record."""
+    device = require_device(getattr(x, "device", None))
+    if x.dim() != 2 or tuple(x.shape) != tuple(y.shape):
+        raise ValueError("x and y must be 2-D and of equal shape")
+    if x.dtype != torch().float64 or y.dtype != torch().float64:
+        raise TypeError("x and y must be float64")
+    if x.stride(1) != 1:
+        x = x.contiguous()
+    if y.stride(1) != 1 or y.stride(0) != x.stride(0):
+        y = y.contiguous()
+        if y.stride(0) != x.stride(0):
+            x = x.contiguous()
+    h, w = x.shape
+    lib = _native.lib()
+    nbytes = lib.xrs_coords_stats_workspace_size(h, w)
+    ws = _workspace(device, nbytes, stream)
+    out = torch().empty(ctypes.sizeof(_native.CoordsStats), dtype=torch().uint8, device=device)
+    rc = lib.xrs_coords_stats(ptr(x), ptr(y), h, w, x.stride(0), 1 if geographic else 0,
+                              ptr(out), ptr(ws), nbytes, stream_handle(device, stream))
+    _native.check(rc, "xrs_coords_stats")
+    if stream is not None:
+        stream.synchronize()   # the read-back below runs on the current stream
+    return CoordsStats(_native.CoordsStats.from_buffer_copy(out.cpu().numpy().tobytes()))
+
+
 # K5a work list: strips of STRIP_H quad rows x STRIP_W quads per tile window
 # (xrs_rectify.hip kStripW / kStripH, one wave per strip)
 STRIP_W, STRIP_H = 63, 16

@@ -24,6 +24,19 @@
     tables, the same values bit for bit).  Default 16 GiB; 0 always fuses.
     Every interpolation method follows this rule ("bicubic" fuses into K1pq).
 
+``coords_device_min_points``:
+    2-D coordinate arrays given to ``GridMapping.from_coords`` /
+    ``from_dataset`` as numpy arrays of at least this many points are uploaded
+    once and analysed on the device (K8, ``kernels.coords_stats``; the upload
+    is kept as the grid mapping's coordinates, so rectification does not
+    upload them again); smaller ones keep the numpy analysis.  Device tensors
+    always take the device path.  Default 1 << 16: measured on an MI355X box
+    (``scripts/time_coords.py``, profiles/coords_stats.jsonl) the device path
+    is already level at 16 384 points (0.53 vs 0.62 ms, inside the spread) and
+    clearly ahead from 65 536 (0.56 vs 1.89 ms; 4000 x 4800: 8.7 ms against
+    0.82 s), so the crossover lies at or below the smallest size timed and
+    the default is the first size with a clear gain.
+
 ``devices``:
     None (default) — every call runs on the current HIP device;
     a list of devices (ordinals or "cuda:k" strings, repeats allowed) —
@@ -40,10 +53,12 @@ from __future__ import annotations
 import contextlib
 
 _OPTIONS = {"reproject_bilinear_dtype": "float64", "host_streaming_min_bytes": 64 << 20,
-            "reproject_table_max_bytes": 16 << 30, "devices": None}
+            "reproject_table_max_bytes": 16 << 30, "coords_device_min_points": 1 << 16,
+            "devices": None}
 _ALLOWED = {"reproject_bilinear_dtype": ("float64", "source"),
             "host_streaming_min_bytes": lambda v: isinstance(v, int) and v >= 0,
             "reproject_table_max_bytes": lambda v: isinstance(v, int) and v >= 0,
+            "coords_device_min_points": lambda v: isinstance(v, int) and v >= 0,
             "devices": lambda v: v is None or _valid_devices(v)}
 
 

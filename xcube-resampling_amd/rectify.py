@@ -138,17 +138,28 @@ def _rectify_dataset(source_ds, target_gm, source_gm, variables, interp_methods,
 def _transform_coords(source_ds: Dataset, source_gm: GridMapping,
                       target_gm: GridMapping) -> Dataset:
     """rectify.py:182-231 — 2-D source coordinates into the target CRS, per
-    point on the device (xrs_transform); the host keeps a copy for the
-    GridMapping analysis of the transformed coordinates."""
+    point on the device (xrs_transform).  Device-resident coordinates, and
+    numpy ones large enough for the device analysis
+    (``coords_device_min_points``), stay on the device as the new coordinates:
+    the GridMapping analysis that follows reads them there (K8); smaller numpy
+    coordinates come back to the host for it."""
     tr = Transformer.from_crs(source_gm.crs, target_gm.crs, always_xy=True)
-    sx, sy = source_gm.x_coords.values, source_gm.y_coords.values
+    sx, sy = source_gm.x_coords.data, source_gm.y_coords.data
+    on_device = is_device_array(sx) and is_device_array(sy)
+    if not on_device:
+        sx, sy = source_gm.x_coords.values, source_gm.y_coords.values
     if tr.is_identity:
-        xx, yy = tr.transform(sx, sy)
+        xx, yy = (to_device(sx, sx.device, np.float64), to_device(sy, sy.device, np.float64)) \
+            if on_device else tr.transform(sx, sy)
     else:
-        shape = np.shape(sx)
-        xd, yd = kernels.transform(tr, np.reshape(sx, (1, -1)), np.reshape(sy, (1, -1)), False,
-                                   require_device())
-        xx, yy = device_to_host(xd).reshape(shape), device_to_host(yd).reshape(shape)
+        shape = tuple(sx.shape)
+        keep = on_device or np.size(sx) >= get_options()["coords_device_min_points"]
+        xd, yd = kernels.transform(tr, sx.reshape(1, -1), sy.reshape(1, -1), False,
+                                   sx.device if on_device else require_device())
+        if keep:
+            xx, yy = xd.reshape(shape), yd.reshape(shape)
+        else:
+            xx, yy = device_to_host(xd).reshape(shape), device_to_host(yd).reshape(shape)
     source_ds = source_ds.drop_vars(source_gm.xy_var_names)
     yx_dims = (source_gm.xy_dim_names[1], source_gm.xy_dim_names[0])
     names = ("lon", "lat") if target_gm.crs.is_geographic else ("transformed_x", "transformed_y")
