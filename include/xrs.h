@@ -533,6 +533,10 @@ int64_t xrs_testing_set(int knob, int64_t value);
                                     both outputs +inf where the satellite does not see
                                     the point                                          */
 #define XRS_PROJ_GEOS_INV 14     /* metres -> degrees; both outputs +inf off the disc   */
+#define XRS_PROJ_AEA_FWD 15      /* aea, ellipsoidal, 1 or 2 parallels: degrees -> metres  */
+#define XRS_PROJ_AEA_INV 16      /* metres -> degrees; +inf, +inf outside the projection   */
+#define XRS_PROJ_SINU_FWD 17     /* sinu, ellipsoid or sphere (es = 0): degrees -> metres  */
+#define XRS_PROJ_SINU_INV 18     /* metres -> degrees; +inf, +inf outside the lobes        */
 
 typedef struct XrsProjStep {
   int32_t kind;      /* XRS_PROJ_* */
@@ -554,9 +558,15 @@ typedef struct XrsProjStep {
                         x0, y0, lam0 and e are read beside them);
                         geos: c[0] radius_g = 1 + h / a, c[1] radius_g_1 = h / a, c[2]
                         radius_g^2 - 1, c[3] sqrt(1 - es), c[4] 1 / (1 - es) (only a, ra,
-                        x0, y0, lam0, one_es and mode are read beside them) */
-  double Qn, Zb;     /* tmerc */
-  double qp, mmf, apa[3], rq, dd, xmf, ymf, sinb1, cosb1;   /* laea */
+                        x0, y0, lam0, one_es and mode are read beside them);
+                        aea: c[0] n, c[1] c, c[2] rho0, c[3] 1 / n, c[4..9] the authalic ->
+                        geodetic latitude series in sin(2 j beta), c[10] n^2 (a, ra, x0, y0,
+                        lam0, e, one_es and qp are read beside them);
+                        sinu: c[0..5] rectifying - geodetic latitude in sin(2 j phi),
+                        c[6..11] the reverse in sin(2 j mu) (a, ra, x0, y0, lam0, es and Qn
+                        are read beside them) */
+  double Qn, Zb;     /* tmerc; sinu: Qn, the meridian arc per radian of mu */
+  double qp, mmf, apa[3], rq, dd, xmf, ymf, sinb1, cosb1;   /* laea; aea: qp */
 } XrsProjStep;
 
 int xrs_transform(const double* x, const double* y, int64_t w, int64_t h, int grid,

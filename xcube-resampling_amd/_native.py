@@ -193,7 +193,8 @@ class ProjStep(ctypes.Structure):
 PROJ_KINDS = {"webmerc_fwd": 1, "webmerc_inv": 2, "tmerc_fwd": 3, "tmerc_inv": 4,
               "laea_fwd": 5, "laea_inv": 6, "stere_fwd": 7, "stere_inv": 8,
               "rotpole_fwd": 9, "rotpole_inv": 10, "lcc_fwd": 11, "lcc_inv": 12,
-              "geos_fwd": 13, "geos_inv": 14}
+              "geos_fwd": 13, "geos_inv": 14, "aea_fwd": 15, "aea_inv": 16,
+              "sinu_fwd": 17, "sinu_inv": 18}
 MAX_PROJ_STEPS = 4
 
 TESTING_KNOBS = {"reproject_band": 1, "reproject_blocks_per_cu": 2, "affine_generic": 3,

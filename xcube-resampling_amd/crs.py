@@ -9,16 +9,17 @@ the small part of PROJ the engine needs:
 * a registry of the CRSs the engine supports (geographic WGS 84 in both axis
   orders, Web Mercator, the UTM zones EPSG:326xx/327xx, LAEA Europe
   EPSG:3035, the polar stereographic grids EPSG:3413 / 3031 / 3995 / 3976,
-  the Lambert conformal conic grids EPSG:3034 / 2154, transverse Mercator /
-  LAEA / polar stereographic / Lambert conformal conic / geostationary CRSs
-  given by CF parameters, and CF rotated-pole grids), with
+  the Lambert conformal conic grids EPSG:3034 / 2154, the Albers equal-area
+  grids EPSG:5070 / 3577 / 3005, transverse Mercator / LAEA / polar
+  stereographic / Lambert conformal conic / Albers / sinusoidal /
+  geostationary CRSs given by CF parameters, and CF rotated-pole grids), with
   the attributes the reference reads (``is_geographic``, ``name``, ``equals``,
   ``to_cf``, ``axis_info``);
 * ``Transformer`` with ``transform`` and ``transform_bounds`` following PROJ's
   formulas: spherical Mercator (``webmerc``: merc_s_forward / merc_s_inverse
   with ``a = 6378137``; coordinates de-scaled by the reciprocal ``ra = 1/a``;
   radians <-> degrees through a precomputed ``unitconvert`` factor), the
-  ellipsoidal ``tmerc``, ``laea``, polar ``stere``, ``lcc`` and ``geos`` and the
+  ellipsoidal ``tmerc``, ``laea``, polar ``stere``, ``lcc``, ``aea``, ``sinu`` and ``geos`` and the
   rotated pole (``ob_tran`` around ``longlat``) of projections.py, and PROJ's
   ``proj_trans_bounds`` edge densification (21 points per edge by default).
 
@@ -60,14 +61,16 @@ class CRS:
     authority: str          # "EPSG", "OGC" or "CF" (defined by CF parameters)
     code: str               # "4326", "CRS84", "3857", "32632", "3035", ...
     name: str
-    # "geographic" | "webmerc" | "tmerc" | "laea" | "stere" | "lcc" | "geos" | "rotated"
+    # "geographic" | "webmerc" | "tmerc" | "laea" | "stere" | "lcc" | "geos" | "aea" |
+    # "sinu" | "rotated"
     kind: str
     axis_order: str         # "latlon" | "lonlat" | "en"
     cf: dict = field(default_factory=dict)
     # projection parameters (tmerc / laea / stere): ellipsoid name, lon_0,
     # lat_0, k0, false easting, false northing; stere adds lat_ts (None:
     # variant A, defined by k0); rotated: ellipsoid name, pole latitude, pole
-    # longitude, north_pole_grid_longitude; lcc adds lat_1, lat_2; geos adds the
+    # longitude, north_pole_grid_longitude; lcc and aea add lat_1, lat_2; sinu adds
+    # its figure's a and rf (rf 0.0: a sphere) at params[6:8]; geos adds the
     # perspective point height, the sweep axis and its ellipsoid's a and rf (the
     # ellipsoid name is "custom" unless they are WGS 84's or GRS 1980's)
     params: tuple = ()
@@ -185,8 +188,11 @@ class CRS:
                 if crs.cf.get("crs_wkt") == wkt:
                     return crs
         if gm_name in ("transverse_mercator", "lambert_azimuthal_equal_area",
-                       "polar_stereographic", "lambert_conformal_conic"):
+                       "polar_stereographic", "lambert_conformal_conic",
+                       "albers_conical_equal_area"):
             return _projected_from_cf(attrs)
+        if gm_name == "sinusoidal":
+            return _sinusoidal_from_cf(attrs)
         if gm_name == "geostationary":
             return _geostationary_from_cf(attrs)
         if gm_name == "latitude_longitude":
@@ -314,6 +320,34 @@ _REGISTRY["EPSG:2154"] = _lcc_crs(
     700000.0, 6600000.0, "RGF93 v1", "Reseau Geodesique Francais 1993 v1")
 _LCC_CODES = ("3034", "2154")
 
+
+def _aea_crs(code: str, name: str, conversion: str, lat_1: float, lat_2: float, lat_0: float,
+             lon_0: float, fe: float, geo: str, datum: str) -> CRS:
+    """A GRS 1980 Albers equal-area CRS with two standard parallels (EPSG method
+    9822), false northing 0."""
+    wkt = (f'PROJCRS["{name}",BASEGEOGCRS["{geo}"],CONVERSION["{conversion}"],'
+           f'ID["EPSG",{code}]]')
+    cf = dict(crs_wkt=wkt, semi_major_axis=_WGS84_A, semi_minor_axis=_GRS80_B,
+              inverse_flattening=298.257222101, reference_ellipsoid_name="GRS 1980",
+              longitude_of_prime_meridian=0.0, prime_meridian_name="Greenwich",
+              geographic_crs_name=geo, horizontal_datum_name=datum,
+              projected_crs_name=name, grid_mapping_name="albers_conical_equal_area",
+              standard_parallel=(lat_1, lat_2), latitude_of_projection_origin=lat_0,
+              longitude_of_central_meridian=lon_0, false_easting=fe, false_northing=0.0)
+    return CRS("EPSG", code, name, "aea", "en", cf,
+               ("GRS 1980", lon_0, lat_0, 1.0, fe, 0.0, lat_1, lat_2))
+
+
+_REGISTRY["EPSG:5070"] = _aea_crs("5070", "NAD83 / Conus Albers", "Conus Albers", 29.5, 45.5,
+                                  23.0, -96.0, 0.0, "NAD83", "North American Datum 1983")
+_REGISTRY["EPSG:3577"] = _aea_crs("3577", "GDA94 / Australian Albers", "Australian Albers",
+                                  -18.0, -36.0, 0.0, 132.0, 0.0, "GDA94",
+                                  "Geocentric Datum of Australia 1994")
+_REGISTRY["EPSG:3005"] = _aea_crs("3005", "NAD83 / BC Albers", "British Columbia Albers", 50.0,
+                                  58.5, 45.0, -126.0, 1000000.0, "NAD83",
+                                  "North American Datum 1983")
+_AEA_CODES = ("5070", "3577", "3005")
+
 _ALIASES = {
     "EPSG:4326": "EPSG:4326", "WGS84": "EPSG:4326", "4326": "EPSG:4326",
     "OGC:CRS84": "OGC:CRS84", "CRS84": "OGC:CRS84", "OGC:1.3:CRS84": "OGC:CRS84",
@@ -321,7 +355,7 @@ _ALIASES = {
     "EPSG:3857": "EPSG:3857", "3857": "EPSG:3857", "EPSG:900913": "EPSG:3857",
     "EPSG:3035": "EPSG:3035", "3035": "EPSG:3035",
 }
-for _code in _POLAR_CODES + _LCC_CODES:
+for _code in _POLAR_CODES + _LCC_CODES + _AEA_CODES:
     _ALIASES[f"EPSG:{_code}"] = _ALIASES[_code] = f"EPSG:{_code}"
 _UTM_CACHE: dict[int, CRS] = {}
 
@@ -355,7 +389,7 @@ def utm_crs(zone: int, south: bool = False) -> CRS:
 
 def _projected_from_cf(attrs: dict) -> CRS:
     """A transverse Mercator / LAEA / polar stereographic / Lambert conformal
-    conic CRS from its CF grid-mapping parameters (the EPSG definition when the
+    conic / Albers CRS from its CF grid-mapping parameters (the EPSG definition when the
     parameters are those of a UTM zone, of EPSG:3035 or of a registered polar
     or conic grid, else a CRS defined by the parameters)."""
     gm = attrs["grid_mapping_name"]
@@ -389,21 +423,23 @@ def _projected_from_cf(attrs: dict) -> CRS:
                 return _REGISTRY[f"EPSG:{code}"]
         return CRS("CF", "stere", attrs.get("projected_crs_name", "Polar Stereographic"),
                    "stere", "en", dict(attrs), params)
-    if gm == "lambert_conformal_conic":
+    if gm in ("lambert_conformal_conic", "albers_conical_equal_area"):
         lon_0 = float(attrs.get("longitude_of_central_meridian", 0.0))
         sp = np.atleast_1d(np.asarray(attrs["standard_parallel"], dtype=np.float64))
         if sp.size not in (1, 2):
-            raise ValueError(f"lambert_conformal_conic needs one or two standard parallels, "
+            raise ValueError(f"{gm} needs one or two standard parallels, "
                              f"was {attrs['standard_parallel']!r}")
         lat_1, lat_2 = float(sp[0]), float(sp[-1])
-        if "latitude_of_projection_origin" not in attrs:
-            lat_0 = lat_1   # PROJ: lat_0 defaults to lat_1
+        lcc = gm == "lambert_conformal_conic"
+        if lcc and "latitude_of_projection_origin" not in attrs:
+            lat_0 = lat_1   # PROJ: lcc's lat_0 defaults to lat_1 (aea's to 0)
         params = (ell, lon_0, lat_0, 1.0, fe, fn, lat_1, lat_2)
-        for code in _LCC_CODES:
+        for code in _LCC_CODES if lcc else _AEA_CODES:
             if params == _REGISTRY[f"EPSG:{code}"].params:
                 return _REGISTRY[f"EPSG:{code}"]
-        return CRS("CF", "lcc", attrs.get("projected_crs_name", "Lambert Conformal Conic"),
-                   "lcc", "en", dict(attrs), params)
+        kind, name = ("lcc", "Lambert Conformal Conic") if lcc else ("aea", "Albers Equal Area")
+        return CRS("CF", kind, attrs.get("projected_crs_name", name), kind, "en", dict(attrs),
+                   params)
     lon_0 = float(attrs.get("longitude_of_projection_origin", 0.0))
     params = (ell, lon_0, lat_0, 1.0, fe, fn)
     if params == _REGISTRY["EPSG:3035"].params:
@@ -451,6 +487,39 @@ def _geostationary_from_cf(attrs: dict) -> CRS:
                              float(attrs["perspective_point_height"]), sweep, a, rf,
                              float(attrs.get("false_easting", 0.0)),
                              float(attrs.get("false_northing", 0.0)))
+
+
+def sinusoidal_crs(lon_0: float = 0.0, a: float = 6371007.181, rf: float | None = None,
+                   false_easting: float = 0.0, false_northing: float = 0.0) -> CRS:
+    """A CF ``sinusoidal`` grid (PROJ ``sinu``) on the figure given by its numbers:
+    semi-major axis ``a`` and inverse flattening ``rf`` (None or 0: a sphere).  The
+    defaults are the MODIS / VIIRS land grid's sphere."""
+    rf = 0.0 if rf is None else float(rf)
+    ell = {(_WGS84_A, _WGS84_RF): "WGS 84", (_WGS84_A, 298.257222101): "GRS 1980"}.get(
+        (a, rf), "sphere" if rf == 0.0 else "custom")
+    cf = dict(grid_mapping_name="sinusoidal", longitude_of_projection_origin=lon_0,
+              false_easting=false_easting, false_northing=false_northing)
+    cf.update(dict(earth_radius=a) if rf == 0.0 else dict(semi_major_axis=a, inverse_flattening=rf))
+    return CRS("CF", "sinu", f"Sinusoidal about {lon_0:g} deg ({ell})", "sinu", "en", cf,
+               (ell, lon_0, 0.0, 1.0, false_easting, false_northing, a, rf))
+
+
+def _sinusoidal_from_cf(attrs: dict) -> CRS:
+    lon_0 = attrs.get("longitude_of_projection_origin",
+                      attrs.get("longitude_of_central_meridian", 0.0))
+    if "earth_radius" in attrs:
+        a, rf = float(attrs["earth_radius"]), None
+    else:
+        a = float(attrs.get("semi_major_axis", _WGS84_A))
+        if "inverse_flattening" in attrs:
+            rf = float(attrs["inverse_flattening"])
+        elif "semi_minor_axis" in attrs:
+            b = float(attrs["semi_minor_axis"])
+            rf = None if b == a else a / (a - b)
+        else:
+            a, rf = _WGS84_A, _WGS84_RF
+    return sinusoidal_crs(float(lon_0), a, rf, float(attrs.get("false_easting", 0.0)),
+                          float(attrs.get("false_northing", 0.0)))
 
 
 def rotated_pole_crs(pole_lat: float, pole_lon: float, pole_grid_lon: float = 0.0) -> CRS:
@@ -527,14 +596,22 @@ def _ellipsoid(name: str):
 
 
 def _conic_or_geos(crs: CRS):
-    """(ellipsoid, projections.py object) of an lcc or geos CRS."""
-    from .projections import Ellipsoid, Geostationary, LambertConformalConic
+    """(ellipsoid, projections.py object) of an lcc, aea, sinu or geos CRS."""
+    from .projections import (AlbersEqualArea, Ellipsoid, Geostationary, LambertConformalConic,
+                              Sinusoidal)
     if crs.kind == "geos":
         height, sweep, a, rf = crs.params[6:10]
         ell = Ellipsoid(crs.params[0], a, rf)
         return ell, Geostationary(ell, height, sweep)
+    if crs.kind == "sinu":
+        a, rf = crs.params[6:8]
+        ell = Ellipsoid(crs.params[0], a, rf if rf else math.inf)   # 1 / inf: f = es = 0
+        return ell, Sinusoidal(ell)
     ell = _ellipsoid(crs.params[0])
     lat_0, k0, lat_1, lat_2 = crs.params[2], crs.params[3], crs.params[6], crs.params[7]
+    if crs.kind == "aea":
+        return ell, AlbersEqualArea(ell, lat_0 * _DEG_TO_RAD, lat_1 * _DEG_TO_RAD,
+                                    lat_2 * _DEG_TO_RAD)
     return ell, LambertConformalConic(ell, lat_0 * _DEG_TO_RAD, lat_1 * _DEG_TO_RAD,
                                       lat_2 * _DEG_TO_RAD, k0)
 
@@ -574,7 +651,7 @@ def _projection(crs: CRS):
         ell = _ellipsoid(ell_name)
         lam0 = lon_0 * _DEG_TO_RAD
         phi0 = lat_0 * _DEG_TO_RAD
-        if crs.kind in ("lcc", "geos"):
+        if crs.kind in ("lcc", "geos", "aea", "sinu"):
             ell, proj = _conic_or_geos(crs)
         elif crs.kind == "stere":
             lat_ts = crs.params[6]
@@ -592,11 +669,11 @@ def _projection(crs: CRS):
             return a * x + x_0, a * y + y_0
 
         def inverse(x, y, proj=proj, lam0=lam0, ra=ra, x_0=x_0, y_0=y_0,
-                    keep_inf=crs.kind == "geos"):
+                    keep_inf=crs.kind in ("geos", "aea", "sinu")):
             xx = (np.asarray(x, dtype=np.float64) - x_0) * ra
             yy = (np.asarray(y, dtype=np.float64) - y_0) * ra
             lam, phi = proj.inverse(xx, yy)
-            if keep_inf:   # off the geos disc both results stay +inf
+            if keep_inf:   # off the geos disc / the sinu lobes / aea's domain: both +inf
                 with np.errstate(invalid="ignore"):
                     lam = np.where(lam == np.inf, lam, _adjlon(lam + lam0))
             else:
@@ -631,7 +708,7 @@ def _proj_step(crs: CRS, inverse: bool):
     ell = _ellipsoid(ell_name)
     st.a, st.ra, st.x0, st.y0 = ell.a, 1.0 / ell.a, x_0, y_0
     st.lam0, st.phi0 = lon_0 * _DEG_TO_RAD, lat_0 * _DEG_TO_RAD
-    if crs.kind in ("lcc", "geos"):
+    if crs.kind in ("lcc", "geos", "aea", "sinu"):
         ell, proj = _conic_or_geos(crs)
         st.a, st.ra = ell.a, 1.0 / ell.a
     st.e, st.es, st.one_es = ell.e, ell.es, ell.one_es
@@ -644,6 +721,16 @@ def _proj_step(crs: CRS, inverse: bool):
         st.mode = 1 if proj.flip else 0
         for k, v in enumerate([proj.radius_g, proj.radius_g_1, proj.C, proj.radius_p,
                                proj.radius_p_inv2]):
+            st.c[k] = v
+    elif crs.kind == "aea":
+        st.kind = PROJ_KINDS["aea_inv" if inverse else "aea_fwd"]
+        st.qp = proj.qp
+        for k, v in enumerate([proj.n, proj.c, proj.rho0, proj.dd] + list(proj.apa) + [proj.n2]):
+            st.c[k] = v
+    elif crs.kind == "sinu":
+        st.kind = PROJ_KINDS["sinu_inv" if inverse else "sinu_fwd"]
+        st.Qn = proj.Qn
+        for k, v in enumerate(list(proj.cmu) + list(proj.cphi)):
             st.c[k] = v
     elif crs.kind == "tmerc":
         proj = TransverseMercator(ell, k0, st.phi0)

@@ -6,7 +6,8 @@
 // transverse Mercator (tmerc poder_engsager: Clenshaw gatg / clenS),
 // Lambert azimuthal equal area (laea e_forward / e_inverse) and polar
 // stereographic (stere e_forward / e_inverse, N_POLE / S_POLE), Lambert conformal
-// conic (lcc, 1SP / 2SP) and the geostationary view (geos, both sweep axes), around
+// conic (lcc, 1SP / 2SP), the geostationary view (geos, both sweep axes), Albers'
+// equal-area conic (aea) and the sinusoidal projection (sinu, sphere included), around
 // PROJ's pj_fwd / pj_inv (lam0 + adjlon, unit-ellipsoid scaling, false origin), and
 // the rotated pole (ob_tran o_forward / o_inverse around longlat).
 // The device libm differs from the host's in the last bit of some
@@ -204,6 +205,14 @@ __device__ inline double qsfn(double sinphi, double e, double one_es) {
 
 // np.clip(v, -1, 1) (NaN stays NaN)
 __device__ inline double clip1(double v) { return v < -1.0 ? -1.0 : (v > 1.0 ? 1.0 : v); }
+
+// pj_qsfn with the logarithm as atanh(e sin phi) (projections.py _qsfn_atanh): qsfn's
+// log of a quotient near 1 is off by an ulp of 1, which 0.5 / e makes 6e-16 of q.
+// laea keeps qsfn (its results are pinned by goldens); aea uses this one.
+__device__ inline double qsfn_atanh(double sinphi, double e, double one_es) {
+  const double con = e * sinphi;
+  return one_es * (sinphi / (1.0 - con * con) + atanh(con) / e);
+}
 
 __device__ inline double authlat(const XrsProjStep& s, double beta) {
   const double t = beta + beta;
@@ -445,6 +454,86 @@ __device__ inline void geos_inv(const XrsProjStep& s, double x, double y, double
   phi = bad ? INFINITY : p;
 }
 
+// ---- Albers equal-area conic (projections.py AlbersEqualArea) -------------------------
+// PROJ aea.cpp on the ellipsoid, one or two standard parallels.  s.c[0]: n; s.c[1]: c;
+// s.c[2]: rho0; s.c[3]: dd = 1 / n; s.c[4..9]: the authalic -> geodetic series in
+// sin(2 j beta); s.c[10]: n^2; s.qp: qsfn(1) (PROJ's ec).  n < 0: the apex lies over the
+// south pole.  The host takes these constants in extended precision.
+// A negative radicand is PROJ's error: both outputs +inf, by a select.
+__device__ inline void aea_fwd(const XrsProjStep& s, double lam, double phi, double& x,
+                               double& y) {
+  const double rad = s.c[1] - s.c[0] * qsfn_atanh(sin(phi), s.e, s.one_es);
+  const bool bad = rad < 0.0;
+  const double rho = s.c[3] * sqrt(bad ? 0.0 : rad);
+  double sinl, cosl;
+  sincos(s.c[0] * lam, &sinl, &cosl);
+  const double xx = rho * sinl;
+  const double yy = s.c[2] - rho * cosl;
+  x = bad ? INFINITY : xx;
+  y = bad ? INFINITY : yy;
+}
+
+// q = (c - n^2 rho^2) / n (rho only through its square: no sqrt) is qp times the sine of the authalic latitude beta, and the
+// geodetic latitude is beta + sum_j A_j sin(2 j beta): six terms whose coefficients
+// the host took per ellipsoid, summed by gatg from sin beta and cos beta (one asin, one
+// sqrt, no logarithm and no division by cos phi), where PROJ's phi1_ iterates up to 15
+// times with a data-dependent exit.  |q| within PROJ's 1e-7 of qp is the pole, |q|
+// beyond it lies outside the projection (+inf, +inf); rho = 0 is PROJ's apex case.
+__device__ inline void aea_inv(const XrsProjStep& s, double x, double y, double& lam,
+                               double& phi) {
+  const double n = s.c[0];
+  y = s.c[2] - y;
+  // |x|, |y| are a few earth radii at most: no scaling needed
+  const double r2 = x * x + y * y;
+  const bool apex = r2 == 0.0;
+  if (n < 0.0) {
+    x = -x;
+    y = -y;
+  }
+  const double q = (s.c[1] - s.c[10] * r2) / n;
+  const bool pole = fabs(s.qp - fabs(q)) <= 1.0e-7;
+  const bool bad = !pole && !apex && fabs(q) > s.qp;
+  const double sb = clip1(q / s.qp);
+  const double cb = sqrt((1.0 - sb) * (1.0 + sb));
+  double ph = gatg(s.c + 4, asin(sb), (cb - sb) * (cb + sb), 2.0 * sb * cb);
+  ph = pole ? copysign(kHalfPi, q) : ph;
+  ph = apex ? (n < 0.0 ? -kHalfPi : kHalfPi) : ph;
+  const double l = apex ? 0.0 : atan2_pp(x, y) * s.c[3];
+  lam = bad ? INFINITY : l;
+  phi = bad ? INFINITY : ph;
+}
+
+// ---- sinusoidal (projections.py Sinusoidal) --------------------------------------------
+// PROJ gn_sinu.cpp sinu on the ellipsoid; the sphere is es = 0, where every series
+// coefficient is 0 and Qn is 1.  The meridian arc is Qn times the rectifying latitude
+// mu.  s.c[0..5]: mu - phi in sin(2 j phi); s.c[6..11]: phi - mu in sin(2 j mu); s.Qn.
+// One Clenshaw sum each way (the forward one from the sine and cosine x needs anyway),
+// where PROJ's pj_inv_mlfn iterates.
+__device__ inline void sinu_fwd(const XrsProjStep& s, double lam, double phi, double& x,
+                                double& y) {
+  double sp, cp;
+  sincos(phi, &sp, &cp);
+  x = lam * cp / sqrt(1.0 - s.es * sp * sp);
+  y = s.Qn * gatg(s.c, phi, (cp - sp) * (cp + sp), 2.0 * sp * cp);
+}
+
+// Outside the lobes (the latitude beyond a pole by 1e-10 or more, or |lam| > pi) both
+// outputs are +inf; within 1e-10 of a pole lam = 0 (x / cos phi has no meaning there).
+__device__ inline void sinu_inv(const XrsProjStep& s, double x, double y, double& lam,
+                                double& phi) {
+  const double mu = y / s.Qn;
+  double s2, c2, sp, cp;
+  sincos(2 * mu, &s2, &c2);
+  const double ph = gatg(s.c + 6, mu, c2, s2);
+  sincos(ph, &sp, &cp);
+  const double away = fabs(ph) - kHalfPi;
+  const bool pole = fabs(away) < kEps10;
+  const double l = pole ? 0.0 : x * sqrt(1.0 - s.es * sp * sp) / cp;
+  const bool bad = away >= kEps10 || fabs(l) > kPi + 1e-12;
+  lam = bad ? INFINITY : l;
+  phi = bad ? INFINITY : ph;
+}
+
 // ---- rotated pole (projections.py RotatedPole) ---------------------------------------
 // s.c[0], s.c[1]: sin / cos of the pole's latitude; s.c[2]: north_pole_grid_longitude;
 // s.lam0: the pole's longitude + 180 deg.  PROJ aatan2 (0 where both vanish: the
@@ -603,7 +692,8 @@ __device__ inline void apply_step(const XrsProjStep& s, double& x, double& y) {
     y = phi * rad_to_deg;
   } else if constexpr (KIND == XRS_PROJ_TMERC_FWD || KIND == XRS_PROJ_LAEA_FWD ||
                        KIND == XRS_PROJ_STERE_FWD || KIND == XRS_PROJ_LCC_FWD ||
-                       KIND == XRS_PROJ_GEOS_FWD) {
+                       KIND == XRS_PROJ_GEOS_FWD || KIND == XRS_PROJ_AEA_FWD ||
+                       KIND == XRS_PROJ_SINU_FWD) {
     const double lam = adjlon(x * kDegToRad - s.lam0);
     const double phi = y * kDegToRad;
     double px, py;
@@ -611,22 +701,30 @@ __device__ inline void apply_step(const XrsProjStep& s, double& x, double& y) {
     else if constexpr (KIND == XRS_PROJ_LAEA_FWD) laea_fwd(s, lam, phi, px, py);
     else if constexpr (KIND == XRS_PROJ_LCC_FWD) lcc_fwd(s, lam, phi, px, py);
     else if constexpr (KIND == XRS_PROJ_GEOS_FWD) geos_fwd(s, lam, phi, px, py);
+    else if constexpr (KIND == XRS_PROJ_AEA_FWD) aea_fwd(s, lam, phi, px, py);
+    else if constexpr (KIND == XRS_PROJ_SINU_FWD) sinu_fwd(s, lam, phi, px, py);
     else stere_fwd(s, lam, phi, px, py);
     x = s.a * px + s.x0;
     y = s.a * py + s.y0;
   } else if constexpr (KIND == XRS_PROJ_TMERC_INV || KIND == XRS_PROJ_LAEA_INV ||
                        KIND == XRS_PROJ_STERE_INV || KIND == XRS_PROJ_LCC_INV ||
-                       KIND == XRS_PROJ_GEOS_INV) {
+                       KIND == XRS_PROJ_GEOS_INV || KIND == XRS_PROJ_AEA_INV ||
+                       KIND == XRS_PROJ_SINU_INV) {
     const double xx = (x - s.x0) * s.ra, yy = (y - s.y0) * s.ra;
     double lam, phi;
     if constexpr (KIND == XRS_PROJ_TMERC_INV) tmerc_inv(s, xx, yy, lam, phi);
     else if constexpr (KIND == XRS_PROJ_LAEA_INV) laea_inv(s, xx, yy, lam, phi);
     else if constexpr (KIND == XRS_PROJ_LCC_INV) lcc_inv(s, xx, yy, lam, phi);
     else if constexpr (KIND == XRS_PROJ_GEOS_INV) geos_inv(s, xx, yy, lam, phi);
+    else if constexpr (KIND == XRS_PROJ_AEA_INV) aea_inv(s, xx, yy, lam, phi);
+    else if constexpr (KIND == XRS_PROJ_SINU_INV) sinu_inv(s, xx, yy, lam, phi);
     else stere_inv(s, xx, yy, lam, phi);
-    // off the geos disc both outputs stay +inf (adjlon would turn the longitude
-    // into NaN, as it does for tmerc and laea, whose results are kept as they are)
-    if constexpr (KIND == XRS_PROJ_GEOS_INV) lam = lam == INFINITY ? lam : adjlon(lam + s.lam0);
+    // off the geos disc, outside aea's domain and outside the sinu lobes both outputs
+    // stay +inf (adjlon would turn the longitude into NaN, as it does for tmerc and
+    // laea, whose results are kept as they are)
+    if constexpr (KIND == XRS_PROJ_GEOS_INV || KIND == XRS_PROJ_AEA_INV ||
+                  KIND == XRS_PROJ_SINU_INV)
+      lam = lam == INFINITY ? lam : adjlon(lam + s.lam0);
     else lam = adjlon(lam + s.lam0);
     x = lam * rad_to_deg;
     y = phi * rad_to_deg;
@@ -640,7 +738,7 @@ __device__ inline void apply_step(const XrsProjStep& s, double& x, double& y) {
 // ---- the pipelines the launch tables take (host) ----------------------------------
 // XRS_PROJ_* kinds come in pairs: odd forward (to the CRS), even inverse
 inline bool is_valid(int kind) {
-  return kind >= XRS_PROJ_WEBMERC_FWD && kind <= XRS_PROJ_GEOS_INV;
+  return kind >= XRS_PROJ_WEBMERC_FWD && kind <= XRS_PROJ_SINU_INV;
 }
 inline bool is_forward(int kind) { return is_valid(kind) && (kind & 1) != 0; }
 
@@ -666,6 +764,8 @@ int dispatch_second(int k1, Fn&& fn) {
     XRS_K1(XRS_PROJ_ROTPOLE_FWD)
     XRS_K1(XRS_PROJ_LCC_FWD)
     XRS_K1(XRS_PROJ_GEOS_FWD)
+    XRS_K1(XRS_PROJ_AEA_FWD)
+    XRS_K1(XRS_PROJ_SINU_FWD)
 #undef XRS_K1
     default: return XRS_ERR_ARG;
   }
@@ -686,6 +786,8 @@ int dispatch_pipeline(int k0, int k1, Fn&& fn) {
     XRS_K0F(XRS_PROJ_ROTPOLE_FWD)
     XRS_K0F(XRS_PROJ_LCC_FWD)
     XRS_K0F(XRS_PROJ_GEOS_FWD)
+    XRS_K0F(XRS_PROJ_AEA_FWD)
+    XRS_K0F(XRS_PROJ_SINU_FWD)
     XRS_K0I(XRS_PROJ_WEBMERC_INV)
     XRS_K0I(XRS_PROJ_TMERC_INV)
     XRS_K0I(XRS_PROJ_LAEA_INV)
@@ -693,6 +795,8 @@ int dispatch_pipeline(int k0, int k1, Fn&& fn) {
     XRS_K0I(XRS_PROJ_ROTPOLE_INV)
     XRS_K0I(XRS_PROJ_LCC_INV)
     XRS_K0I(XRS_PROJ_GEOS_INV)
+    XRS_K0I(XRS_PROJ_AEA_INV)
+    XRS_K0I(XRS_PROJ_SINU_INV)
 #undef XRS_K0F
 #undef XRS_K0I
     default: return XRS_ERR_ARG;

@@ -20,6 +20,11 @@ PROJ's ``pj_fwd`` / ``pj_inv`` do):
   parallels (EPSG methods 9801 / 9802; EPSG:3034, EPSG:2154);
 * ``Geostationary`` — PROJ ``geos`` on the ellipsoid, both sweep axes (CF
   ``geostationary``);
+* ``AlbersEqualArea`` — PROJ ``aea`` on the ellipsoid, one or two standard
+  parallels, either hemisphere (EPSG:5070, 3577, 3005; CF
+  ``albers_conical_equal_area``);
+* ``Sinusoidal`` — PROJ ``sinu`` on the ellipsoid, the sphere as its es = 0 case
+  (the MODIS / VIIRS land grid; CF ``sinusoidal``);
 * ``RotatedPole`` — PROJ ``ob_tran +o_proj=longlat`` as CF's
   ``rotated_latitude_longitude`` defines it (degrees on both sides).
 
@@ -523,6 +528,176 @@ class Geostationary:
         Vz = Vz * k
         lam = np.arctan2(Vy, Vx)
         phi = np.arctan2(self.radius_p_inv2 * Vz, np.sqrt(Vx * Vx + Vy * Vy))
+        return np.where(bad, np.inf, lam), np.where(bad, np.inf, phi)
+
+
+# ---- Albers equal-area conic (PROJ aea.cpp on the ellipsoid) ------------------------
+_TOL7 = 1.0e-7
+
+
+def _qsfn_atanh(sinphi, e, one_es):
+    """pj_qsfn with the logarithm as atanh(e sin phi): ``_qsfn``'s log of a quotient
+    near 1 carries an absolute error of an ulp of 1, which its factor 0.5 / e = 6
+    makes 6e-16 of q; that is 2e-15 of the cone constant n and 3e-8 m at the far
+    pole.  laea keeps ``_qsfn`` (its results are pinned); aea uses this one."""
+    con = e * sinphi
+    return one_es * (sinphi / (1.0 - con * con) + np.arctanh(con) / e)
+
+
+def _sine_series(fn, order: int = _ORDER, samples: int = 32):
+    """The first ``order`` coefficients of the odd, pi-periodic ``fn`` as a series
+    sum_j A_j sin(2 j t), by the midpoint sine transform over (0, pi/2).  The
+    auxiliary-latitude differences have coefficients of size n^j, so aliasing
+    (from j = 2 samples -+ j on) and the truncation lie below 1e-20."""
+    t = (np.arange(samples) + 0.5) * (_HALFPI / samples)
+    g = fn(t)
+    return [float(2.0 / samples * np.sum(g * np.sin(2 * j * t))) for j in range(1, order + 1)]
+
+
+def _authalic_to_geodetic(ell: Ellipsoid):
+    """phi - beta = sum_j A_j sin(2 j beta), j = 1..6: the authalic -> geodetic
+    latitude series, its coefficients taken numerically per ellipsoid (Newton on
+    q(phi) = qp sin beta, Snyder (3-16), run to convergence at the sample points
+    when the CRS is made, never per point)."""
+    e, es, one_es = ell.e, ell.es, ell.one_es
+    qp = float(_qsfn_atanh(1.0, e, one_es))
+
+    def diff(beta):
+        q, phi = qp * np.sin(beta), beta.copy()
+        for _ in range(8):   # quadratic from an error of es / 3: exact after 4
+            s = np.sin(phi)
+            con = 1.0 - es * s * s
+            phi = phi + con * con / (2.0 * np.cos(phi)) * ((q - _qsfn_atanh(s, e, one_es)) / one_es)
+        return phi - beta
+
+    return _sine_series(diff)
+
+
+class AlbersEqualArea:
+    """PROJ aea, ellipsoidal (aea.cpp e_forward / e_inverse).  ``phi1 == phi2`` is
+    the one-parallel form; n < 0 puts the apex over the south pole.  The inverse
+    takes the latitude from q = (c - (rho n)^2) / n through the authalic latitude
+    beta (sin beta = q / qp) and a 6-term sine series in 2 beta (``apa``), in place of
+    PROJ's ``phi1_`` iteration; |q| within PROJ's 1e-7 of qp is the pole, |q|
+    beyond that is outside the projection: both results +inf."""
+
+    def __init__(self, ell: Ellipsoid, phi0: float, phi1: float, phi2: float):
+        if abs(phi1 + phi2) < _EPS10:
+            raise ValueError("AlbersEqualArea: lat_1 = -lat_2 is no cone")
+        self.ell = ell
+        # The constants are PROJ's, taken in extended precision and rounded once: n is
+        # a quotient of two differences (m1^2 - m2^2 and q2 - q1 cancel a digit each), and
+        # in float64 its error of 1e-15 is 2e-8 m at the far pole and 2e-12 deg in the
+        # inverse next to a pole, where q is flat.  (Where long double is float64 the
+        # constants are merely float64's.)
+        ld = np.longdouble
+        es = ld(ell.es)
+        e, one_es = np.sqrt(es), 1.0 - es
+
+        def msq(phi):   # pj_msfn squared
+            return np.cos(ld(phi)) ** 2 / (1.0 - es * np.sin(ld(phi)) ** 2)
+
+        def qs(phi):
+            return _qsfn_atanh(np.sin(ld(phi)), e, one_es)
+
+        n, ml1 = np.sin(ld(phi1)), qs(phi1)
+        if abs(phi1 - phi2) >= _EPS10:   # secant cone
+            n = (msq(phi1) - msq(phi2)) / (qs(phi2) - ml1)
+        c = msq(phi1) + n * ml1
+        self.n, self.dd, self.n2, self.c = float(n), float(1.0 / n), float(n * n), float(c)
+        self.qp = float(qs(_HALFPI))                    # PROJ's ec
+        self.rho0 = float(np.sqrt(c - n * qs(phi0)) / n)
+        self.apa = _authalic_to_geodetic(ell)
+
+    def forward(self, lam, phi):
+        lam = np.asarray(lam, dtype=np.float64)
+        phi = np.asarray(phi, dtype=np.float64)
+        rad = self.c - self.n * _qsfn_atanh(np.sin(phi), self.ell.e, self.ell.one_es)
+        with np.errstate(invalid="ignore"):
+            bad = rad < 0.0
+        rho = self.dd * np.sqrt(np.where(bad, 0.0, rad))
+        nl = self.n * lam
+        x = rho * np.sin(nl)
+        y = self.rho0 - rho * np.cos(nl)
+        return np.where(bad, np.inf, x), np.where(bad, np.inf, y)
+
+    def inverse(self, x, y):
+        n = self.n
+        x = np.asarray(x, dtype=np.float64)
+        y = self.rho0 - np.asarray(y, dtype=np.float64)
+        r2 = x * x + y * y             # a few earth radii at most: no scaling
+        apex = r2 == 0.0
+        if n < 0.0:
+            x, y = -x, -y
+        q = (self.c - self.n2 * r2) / n   # rho only through its square: no sqrt
+        with np.errstate(invalid="ignore"):
+            pole = np.abs(self.qp - np.abs(q)) <= _TOL7
+            bad = ~pole & ~apex & (np.abs(q) > self.qp)
+            sb = np.clip(q / self.qp, -1.0, 1.0)
+            cb = np.sqrt((1.0 - sb) * (1.0 + sb))
+            phi = _gatg(self.apa, np.arcsin(sb), (cb - sb) * (cb + sb), 2.0 * sb * cb)
+            phi = np.where(pole, np.copysign(_HALFPI, q), phi)
+            lam = np.where(apex, 0.0, np.arctan2(x, y) * self.dd)
+        phi = np.where(apex, -_HALFPI if n < 0.0 else _HALFPI, phi)
+        return np.where(bad, np.inf, lam), np.where(bad, np.inf, phi)
+
+
+# ---- Sinusoidal (PROJ gn_sinu.cpp sinu on the ellipsoid; the sphere is es = 0) -------
+def _rectifying_series(ell: Ellipsoid):
+    """(cmu, cphi): mu - phi = sum_j cmu_j sin(2 j phi) and phi - mu = sum_j cphi_j
+    sin(2 j mu), j = 1..6, the geodetic <-> rectifying latitude series in the third
+    flattening n (Karney 2011, eqs. 35-36 extended to n^6).  The meridian arc from
+    the equator is M(phi) = Qn mu with tmerc's Qn at k0 = 1; at es = 0 every
+    coefficient is 0."""
+    f = ell.es / (1.0 + math.sqrt(1.0 - ell.es))
+    n = f / (2.0 - f)
+    n2 = n * n
+    n3, n4, n5, n6 = n2 * n, n2 * n2, n2 * n2 * n, n2 * n2 * n2
+    cmu = [-3 / 2.0 * n + 9 / 16.0 * n3 - 3 / 32.0 * n5,
+           15 / 16.0 * n2 - 15 / 32.0 * n4 + 135 / 2048.0 * n6,
+           -35 / 48.0 * n3 + 105 / 256.0 * n5,
+           315 / 512.0 * n4 - 189 / 512.0 * n6,
+           -693 / 1280.0 * n5,
+           1001 / 2048.0 * n6]
+    cphi = [3 / 2.0 * n - 27 / 32.0 * n3 + 269 / 512.0 * n5,
+            21 / 16.0 * n2 - 55 / 32.0 * n4 + 6759 / 4096.0 * n6,
+            151 / 96.0 * n3 - 417 / 128.0 * n5,
+            1097 / 512.0 * n4 - 15543 / 2560.0 * n6,
+            8011 / 2560.0 * n5,
+            293393 / 61440.0 * n6]
+    return cmu, cphi
+
+
+class Sinusoidal:
+    """PROJ sinu, ellipsoidal (gn_sinu.cpp e_forward / e_inverse): x = lam cos phi /
+    sqrt(1 - es sin^2 phi), y = the meridian arc M(phi).  The arc and its inverse
+    are one 6-term Clenshaw sum each over the rectifying latitude (no
+    ``pj_inv_mlfn`` iteration).  Outside the lobes (|y| beyond the pole's arc or
+    |lam| > pi) both results are +inf; within 1e-10 of a pole lam = 0."""
+
+    def __init__(self, ell: Ellipsoid):
+        self.ell = ell
+        self.Qn = TransverseMercator(ell, 1.0).Qn
+        self.cmu, self.cphi = _rectifying_series(ell)
+
+    def forward(self, lam, phi):
+        lam = np.asarray(lam, dtype=np.float64)
+        phi = np.asarray(phi, dtype=np.float64)
+        s, c = np.sin(phi), np.cos(phi)
+        x = lam * c / np.sqrt(1.0 - self.ell.es * s * s)
+        y = self.Qn * _gatg(self.cmu, phi, (c - s) * (c + s), 2.0 * s * c)
+        return x, y
+
+    def inverse(self, x, y):
+        x = np.asarray(x, dtype=np.float64)
+        mu = np.asarray(y, dtype=np.float64) / self.Qn
+        with np.errstate(invalid="ignore"):
+            phi = _gatg(self.cphi, mu, np.cos(2 * mu), np.sin(2 * mu))
+            s, c = np.sin(phi), np.cos(phi)
+            away = np.abs(phi) - _HALFPI
+            pole = np.abs(away) < _EPS10
+            lam = np.where(pole, 0.0, x * np.sqrt(1.0 - self.ell.es * s * s) / c)
+            bad = (away >= _EPS10) | (np.abs(lam) > math.pi + 1e-12)
         return np.where(bad, np.inf, lam), np.where(bad, np.inf, phi)
 
 
